@@ -2,8 +2,14 @@
 """North-star benchmark: pod-fail → checkpoint latency (p50/p99) and events/s at
 10k concurrent jobs (BASELINE.json ``metric``), one supervised GPU-job slot per rank.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--jobs 10000] [--events 1000]
-                    [--transport wire|inproc] [--profile uncapped|reference]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--jobs 10000]
+                    [--events 1000] [--transport wire|inproc] [--profile uncapped|reference]
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line.  ``--full``
+adds what the headline figure does not need: a real HBM-OOM on the rank's GPU for the synthetic
+failures' text, the open-loop latency probe, the read-back of every timed row from the store
+and the GPU monitor's cost per sample.  ``--dump-outputs DIR``
+writes what the last timed step left in the store as ``DIR/<name>.npy``.
 
 One process per GPU (``torch.distributed.run`` for N>1).  Each rank runs one
 supervisor replica that owns the shard of runs hashed to it (``sharding``), split
@@ -48,6 +54,16 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: a real HBM-OOM on the rank's "
+                         "GPU whose text the synthetic hbm-oom failures carry (real_hbm_oom), the open-loop latency "
+                         "probe (--probe-events, latency_at_rate), the read-back of every timed row from the store "
+                         "(readback) and the GPU monitor's CPU per sample (config.monitor)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write DIR/<name>.npy (float32): the lifecycle stage the store holds "
+                         "for every run the last timed step failed (last_step_failed_stage) and started "
+                         "(last_step_started_stage), numbered as bench/runner.py STAGE_CODES, in the seeded "
+                         "workload's order")
     ap.add_argument("--jobs", type=int, default=None,
                     help="concurrent live jobs per rank (default 10,000; node mode: 10,000 over the node's slots)")
     ap.add_argument("--events", type=int, default=None,
@@ -66,10 +82,12 @@ def parse_args(argv=None):
                     help="generate each step's synthetic traffic on demand instead of before the timed region")
     ap.add_argument("--kube-connections", type=int, default=256)
     ap.add_argument("--probe-events", type=int, default=600,
-                    help="after the timed steps: open-loop latency probe with this many single failures, Poisson "
+                    help="--full, after the timed steps: open-loop latency probe with this many single failures, Poisson "
                          "arrivals (0 = off); 600 at 1000/min take ~36 s and make p99 a real quantile")
     ap.add_argument("--probe-rate", type=float, default=1000.0, help="probe rate, pod failures per minute (BASELINE config 4)")
-    ap.add_argument("--no-real-oom", action="store_true", help="skip the real HBM-OOM on the rank's GPU")
+    ap.add_argument("--no-real-oom", action="store_true",
+                    help="--full: skip the real HBM-OOM on the rank's GPU (its message and VRAM peak seed the synthetic "
+                         "hbm-oom failures; a plain run uses the recorded text of one, workload.DEFAULT_HIP_OOM)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--json-out", default="")
     ap.add_argument("--pprof-out", default="", help="write a pprof profile of the timed steps (rank 0)")
@@ -276,12 +294,14 @@ def main(argv=None) -> int:
         dist.init_process_group(backend=backend)
     device = torch.device(f"cuda:{local_rank}") if has_gpu else torch.device("cpu")
 
-    from nexus_supervisor_amd.bench.runner import BenchConfig, run_rank
+    from nexus_supervisor_amd.bench.runner import BenchConfig, mark, run_rank
 
+    mark("torch imported, device chosen")
     workdir = tempfile.mkdtemp(prefix=f"nexus-bench-r{rank}-")
     hip_msg = None
-    if has_gpu and not args.no_real_oom:
+    if has_gpu and args.full and not args.no_real_oom:
         hip_msg = real_hbm_oom(local_rank, workdir)
+        mark("real HBM-OOM done")
 
     def barrier_sync():
         if dist is not None:
@@ -331,8 +351,16 @@ def main(argv=None) -> int:
                       pregen=not args.no_pregen, cluster=cluster, run_starts=args.workload == "lifecycle",
                       pprof_out=args.pprof_out if rank == 0 else "", pprof_hz=args.pprof_hz, slot_mode=slot_mode,
                       gpu_evidence=args.gpu_evidence, probe_timeline=args.diag_probe_timeline,
-                      step_timeline=args.diag_step_timeline)
+                      step_timeline=args.diag_step_timeline, full=args.full, dump_outputs=bool(args.dump_outputs))
     res = asyncio.run(run_rank(cfg, barrier_sync, share, oom_phase if slot_mode == "node" and world > 1 else None))
+
+    if args.dump_outputs and res.get("outputs"):
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, values in res["outputs"].items():  # a few thousand numbers each
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"),
+                    np.asarray(values, dtype=np.float32))
 
     elapsed = res["elapsed"]
     rb = res.get("readback") or {}
@@ -444,6 +472,7 @@ def main(argv=None) -> int:
                 "parallelism": (f"node{world}slots:1replica:{args.procs}proc" if cluster == "node" else
                                 f"shard{world}x{args.procs if args.transport == 'wire' else 1}proc"),
                 "slot_mode": slot_mode,
+                "full": args.full,
                 "cpu_affinity": placed,
                 # GPU monitors over the node's GPUs: one (rank 0's, the node agent's role) in
                 # node mode, one per rank otherwise

@@ -124,6 +124,10 @@ async def amain(args) -> None:
         if node_slots:
             indexes = list(range(node_slots))  # node mode: one workload per GPU slot, one replica
         total = 0
+        # building the namespace and the pre-generated steps allocates millions of dicts that
+        # reference counting alone frees: the collector's passes over that growing heap were
+        # more than half of this request's time.  Collected once and re-enabled below
+        gc.disable()
         for k in indexes:
             # per-rank mode: the rank's workload (rank = its shard); shared mode: one per shard;
             # node mode: slot k's runs on GPU k (one replica owns every slot: no shard filter)
@@ -155,6 +159,7 @@ async def amain(args) -> None:
         gc.collect()
         gc.freeze()
         gc.set_threshold(20000, 20, 20)
+        gc.enable()
         return web.json_response({"objects": total, "shards": sorted(shards)})
 
     async def prepare(wl, events: int):

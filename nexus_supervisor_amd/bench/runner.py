@@ -75,6 +75,11 @@ class BenchConfig:
     # process annotates failed pods and the supervisor waits gpu.evidence-wait for it
     gpu_evidence: str = "local"
     evidence_wait: float = 2.0
+    # everything beside the timed steps' own figures: the GPU monitor's cost per sample, the
+    # read-back of every timed row and the open-loop latency probe (``bench.py --full``)
+    full: bool = True
+    # keep what the last timed step left in the store (``bench.py --dump-outputs``)
+    dump_outputs: bool = False
 
     @property
     def node(self) -> bool:
@@ -309,6 +314,17 @@ class InProcHarness:
         return {}
 
 
+_T_START = time.monotonic()
+
+
+def mark(what: str) -> None:
+    """``NEXUS_BENCH_DEBUG``: seconds since the bench was imported, at each phase's end (stderr)."""
+    if os.environ.get("NEXUS_BENCH_DEBUG"):
+        import sys
+
+        print(f"[bench] +{time.monotonic() - _T_START:.2f}s {what}", file=sys.stderr, flush=True)
+
+
 def _dump_tasks_on_sigusr2() -> None:
     """Diagnostics: ``kill -USR2 <rank pid>`` prints every pending asyncio task's stack."""
     import signal
@@ -416,7 +432,7 @@ async def run_rank(cfg: BenchConfig, barrier_sync: Callable[[], None],
     # agent mode: the real monitor is the agent's (its own process); the runner's is a stand-in
     telemetry = make_telemetry(cfg.telemetry) if cfg.telemetry != "fake" and not via_agent else FakeTelemetry()
     telemetry.start()
-    monitor = await asyncio.get_running_loop().run_in_executor(None, monitor_cost, telemetry)
+    monitor = await asyncio.get_running_loop().run_in_executor(None, monitor_cost, telemetry) if cfg.full else None
     if cfg.transport == "inproc":
         harness = InProcHarness(sc, cfg)
     else:
@@ -427,8 +443,10 @@ async def run_rank(cfg: BenchConfig, barrier_sync: Callable[[], None],
     sampler = None
     agent = None
     beat = None
+    mark("telemetry started")
     try:
         await harness.start()
+        mark("harness started")
         sup = harness.supervisor
         if via_agent:
             from .agentproc import AgentProcess
@@ -446,6 +464,7 @@ async def run_rank(cfg: BenchConfig, barrier_sync: Callable[[], None],
             sup.decision_hooks.append(tracker)
 
         done_at: List[float] = []  # completion time of each timed step (diagnostics)
+        last_docs: List[Dict[str, Any]] = []  # the last step pushed (--dump-outputs)
 
         async def run_steps(n: int) -> None:
             """Push ``n`` steps with at most ``cfg.inflight`` unacknowledged at a time."""
@@ -464,8 +483,9 @@ async def run_rank(cfg: BenchConfig, barrier_sync: Callable[[], None],
                     for st in pending.pop(0):
                         await finish(st)
                 docs = await harness.step(cfg.events)
+                last_docs[:] = docs if isinstance(docs, list) else [docs]
                 pending.append([tracker.arm(d["rids"], d["t_push"], d.get("expected"), d.get("started"),
-                                            d.get("start_expected")) for d in (docs if isinstance(docs, list) else [docs])])
+                                            d.get("start_expected")) for d in last_docs])
             for sts in pending:
                 for st in sts:
                     await finish(st)
@@ -484,6 +504,7 @@ async def run_rank(cfg: BenchConfig, barrier_sync: Callable[[], None],
 
         beat = asyncio.ensure_future(heartbeat())
         await run_steps(cfg.warmup)
+        mark("warmup done")
         phase.update(name="timed", t0=time.monotonic())
         gc.collect()
         tracker.errors = tracker.wrong_stage = 0
@@ -514,6 +535,7 @@ async def run_rank(cfg: BenchConfig, barrier_sync: Callable[[], None],
             await step_tl.stop()
         barrier_sync()
         elapsed = time.perf_counter() - t0
+        mark("timed steps done")
         timed = (tracker.failures, tracker.starts, list(tracker.start_latencies))
         step_done_ms = [round(1000.0 * (t - t0), 1) for t in done_at]
         step_timeline = None
@@ -627,14 +649,15 @@ async def run_rank(cfg: BenchConfig, barrier_sync: Callable[[], None],
                             # default pods: the agent read their OOM text from the node's logs
                             "agent_log_reads": int(sum(v for k, v in am.items() if k.endswith("agent_log_reads_total"))),
                             "supervisor_log_fetches": int(sup.metrics.counter("decisions_deferred_for_log_tail"))}
+        outputs = await _last_step_outputs(harness, last_docs) if cfg.dump_outputs and cfg.steps > 0 else None
         phase.update(name="readback", t0=time.monotonic())
-        readback = await _read_back(harness, tracker)
+        readback = await _read_back(harness, tracker) if cfg.full else {"checked": 0}
         attribution = None
         if cfg.node and oom_phase is not None:
             ooms = await asyncio.get_running_loop().run_in_executor(None, oom_phase)
             attribution = await _node_attribution(harness, tracker, telemetry, ooms, cfg)
         probe = None
-        if cfg.probe_events > 0:
+        if cfg.full and cfg.probe_events > 0:
             before = _stage_counts(sup)
             slow0 = _slow_snapshot(sup)
             phase.update(name="probe", t0=time.monotonic())
@@ -647,6 +670,7 @@ async def run_rank(cfg: BenchConfig, barrier_sync: Callable[[], None],
                 slow = _slow_callbacks(slow0, _slow_snapshot(sup))
                 if slow:  # NEXUS_SLOW_CALLBACK_MS: what held a loop during the probe
                     probe["slow_callbacks"] = slow
+        mark("measured")
     finally:
         if beat is not None:
             beat.cancel()
@@ -659,6 +683,7 @@ async def run_rank(cfg: BenchConfig, barrier_sync: Callable[[], None],
         if monitor is not None:
             # libamd_smi's "Unable to open queues directory" lines, counted instead of printed
             monitor["process_vanished"] = telemetry.process_vanished()
+        mark("stopped")
     return {"elapsed": elapsed, "events": cfg.events * cfg.steps * (cfg.world if cfg.node else 1), "errors": tracker.errors,
             "failures": timed[0], "starts": timed[1], "start_latencies_ms": timed[2],
             "starts_superseded": tracker.superseded,
@@ -668,7 +693,7 @@ async def run_rank(cfg: BenchConfig, barrier_sync: Callable[[], None],
             "actuation": _actuation(sc),
             "eps": sc.rate_limit_elements_per_second, "kube_qps": sc.kube_qps, "telemetry": telemetry.name, "stages": stages, "cpu": cpu,
             "probe": probe, "step_done_ms": step_done_ms, "monitor": monitor, "attribution": attribution,
-            "gpu_evidence": gpu_evidence, "step_timeline": step_timeline}
+            "gpu_evidence": gpu_evidence, "step_timeline": step_timeline, "outputs": outputs}
 
 
 async def _latency_probe(harness, tracker: "Tracker", cfg: "BenchConfig") -> Dict[str, Any]:
@@ -1013,6 +1038,23 @@ def decompose(parts) -> Dict[str, Any]:
     out["median_band_mean_ms"] = band(0.45, 0.55)
     out["tail_p99_mean_ms"] = band(0.99, 1.0)
     return out
+
+
+# the number a lifecycle stage is written as in a dumped output (-1: no row)
+STAGE_CODES = {s: float(i) for i, s in enumerate(("NEW", "BUFFERED", "RUNNING", "COMPLETED", "FAILED", "SCHEDULING_FAILED",
+                                                  "DEADLINE_EXCEEDED", "CANCELLED"))}
+
+
+async def _last_step_outputs(harness, docs: List[Dict[str, Any]]) -> Dict[str, List[float]]:
+    """What the timed path left behind in its last step: the lifecycle stage the store holds
+    for every run that step failed and for every run it started, as :data:`STAGE_CODES`, in
+    the order the (seeded) workload generated them — the same runs in the same order for the
+    same arguments, whatever order the decisions were taken in."""
+    failed = [r for d in docs for r in d["rids"]]
+    started = [r for d in docs for r in d.get("started") or ()]
+    got = await harness.read_stages(harness.algorithm, failed + started)
+    code = lambda r: STAGE_CODES.get(got.get(r), -1.0)  # noqa: E731
+    return {"last_step_failed_stage": [code(r) for r in failed], "last_step_started_stage": [code(r) for r in started]}
 
 
 async def _read_back(harness, tracker: "Tracker") -> Dict[str, Any]:

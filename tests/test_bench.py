@@ -47,7 +47,7 @@ def test_bench_wire_in_process(tmp_path, capsys):
     import bench
 
     js = tmp_path / "b.json"
-    rc = bench.main(["--steps", "2", "--warmup", "1", "--jobs", "300", "--events", "60", "--probe-events", "3",
+    rc = bench.main(["--full", "--steps", "2", "--warmup", "1", "--jobs", "300", "--events", "60", "--probe-events", "3",
                      "--probe-rate", "6000", "--json-out", str(js)])
     assert rc == 0
     lines = [x for x in capsys.readouterr().out.splitlines() if x.startswith("{")]
@@ -70,6 +70,36 @@ def test_bench_wire_in_process(tmp_path, capsys):
 
 
 @pytest.mark.slow
+def test_bench_plain_run_is_lean_and_dumps_the_last_steps_rows(tmp_path, capsys):
+    """Without ``--full`` the line holds the timed steps' figures only (no probe, no read-back,
+    no monitor cost); ``--dump-outputs`` writes the stages the store holds for the last timed
+    step's runs, identical from run to run for the same arguments."""
+    import numpy as np
+
+    import bench
+    from nexus_supervisor_amd.bench.runner import STAGE_CODES
+
+    dumps = []
+    for d in ("a", "b"):
+        rc = bench.main(["--steps", "3", "--warmup", "1", "--jobs", "200", "--events", "30", "--procs", "1",
+                         "--dump-outputs", str(tmp_path / d)])
+        assert rc == 0
+        out = json.loads([x for x in capsys.readouterr().out.splitlines() if x.startswith("{")][-1])
+        assert KEYS <= set(out) and out["steps"] == 3 and out["value"] > 0 and out["errors"] == 0
+        assert out["ms_per_step"] > 0 and abs(out["value"] * out["ms_per_step"] / 1000.0 - 30) < 0.5
+        assert out["latency_at_rate"] is None and out["readback"]["checked"] == 0 and out["config"]["monitor"] is None
+        assert out["wrong_stage"] == 0 and out["config"]["full"] is False
+        assert sorted(os.listdir(tmp_path / d)) == ["last_step_failed_stage.npy", "last_step_started_stage.npy"]
+        dumps.append({n: np.load(tmp_path / d / n) for n in os.listdir(tmp_path / d)})
+    a, b = dumps
+    failed, started = a["last_step_failed_stage.npy"], a["last_step_started_stage.npy"]
+    assert failed.dtype == np.float32 and failed.shape == (30,) and 0 < started.size <= 30
+    terminal = {STAGE_CODES[s] for s in ("FAILED", "SCHEDULING_FAILED", "DEADLINE_EXCEEDED")}
+    assert set(failed.tolist()) <= terminal and set(started.tolist()) == {STAGE_CODES["RUNNING"]}
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+
+
+@pytest.mark.slow
 def test_bench_gpu_evidence_through_the_node_agent(capsys):
     """``--gpu-evidence agent``: the node agent as its own process annotates every failed GPU
     pod (default pods: their logs read from a kubelet-style /var/log/pods the simulator
@@ -77,7 +107,7 @@ def test_bench_gpu_evidence_through_the_node_agent(capsys):
     the agent's cost and how many waits expired, and every row still reads back correct."""
     import bench
 
-    rc = bench.main(["--steps", "2", "--warmup", "1", "--jobs", "300", "--events", "40", "--probe-events", "5",
+    rc = bench.main(["--full", "--steps", "2", "--warmup", "1", "--jobs", "300", "--events", "40", "--probe-events", "5",
                      "--probe-rate", "6000", "--gpu-evidence", "agent", "--procs", "2"])
     assert rc == 0
     out = json.loads([x for x in capsys.readouterr().out.splitlines() if x.startswith("{")][-1])
@@ -98,7 +128,7 @@ def test_bench_fused_actuation_with_priced_lwt(capsys):
     where the two-step path's write costs 1 (+1 read)."""
     import bench
 
-    rc = bench.main(["--steps", "2", "--warmup", "1", "--jobs", "300", "--events", "40", "--probe-events", "0",
+    rc = bench.main(["--full", "--steps", "2", "--warmup", "1", "--jobs", "300", "--events", "40", "--probe-events", "0",
                      "--actuation", "fused", "--cql-latency-us", "2000", "--procs", "1"])
     assert rc == 0
     out = json.loads([x for x in capsys.readouterr().out.splitlines() if x.startswith("{")][-1])
@@ -115,7 +145,7 @@ def test_bench_two_step_write_ab(capsys):
     the line says which actuation it measured."""
     import bench
 
-    rc = bench.main(["--steps", "2", "--warmup", "1", "--jobs", "300", "--events", "60", "--probe-events", "0",
+    rc = bench.main(["--full", "--steps", "2", "--warmup", "1", "--jobs", "300", "--events", "60", "--probe-events", "0",
                      "--two-step-write"])
     assert rc == 0
     out = json.loads([x for x in capsys.readouterr().out.splitlines() if x.startswith("{")][-1])
@@ -132,7 +162,7 @@ def test_bench_two_ranks_torchrun_gloo():
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
-                        "--steps", "2", "--warmup", "1", "--jobs", "200", "--events", "40", "--transport", "inproc",
+                        "--full", "--steps", "2", "--warmup", "1", "--jobs", "200", "--events", "40", "--transport", "inproc",
                         "--probe-events", "0"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.startswith("{")]
@@ -155,7 +185,7 @@ def test_bench_two_ranks_wire_worker_processes():
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
-                        "--steps", "2", "--warmup", "1", "--jobs", "300", "--events", "50", "--procs", "2",
+                        "--full", "--steps", "2", "--warmup", "1", "--jobs", "300", "--events", "50", "--procs", "2",
                         "--probe-events", "0", "--cluster", "shared", "--slot-mode", "replica"], cwd=ROOT, env=env,
                        capture_output=True,
                        text=True, timeout=300)
@@ -211,7 +241,7 @@ def test_bench_four_ranks_shared_cluster_not_harness_bound():
     + one CQL server, four replicas each owning a shard of the namespace): no harness
     process saturated, every decision in its expected stage, every timed row read back,
     and the replica CPU per failure reported for every rank."""
-    out = _torchrun(4, "--steps", "2", "--warmup", "1", "--jobs", "200", "--events", "30", "--procs", "1",
+    out = _torchrun(4, "--full", "--steps", "2", "--warmup", "1", "--jobs", "200", "--events", "30", "--procs", "1",
                     "--probe-events", "0", "--cluster", "shared", "--slot-mode", "replica")
     _check(out, 4, 2, 1, 30)
     assert out["config"]["cluster"] == "shared" and out["config"]["parallelism"] == "shard4x1proc"
@@ -226,7 +256,7 @@ def test_bench_two_ranks_per_rank_clusters_and_poisson_probe():
     """The default N>1 layout: every GPU-job slot's replica with its own apiserver simulator
     and CQL server (weak scaling with nothing shared), plus the open-loop probe: Poisson
     arrivals, every probe event acknowledged."""
-    out = _torchrun(2, "--steps", "2", "--warmup", "1", "--jobs", "200", "--events", "30", "--procs", "1",
+    out = _torchrun(2, "--full", "--steps", "2", "--warmup", "1", "--jobs", "200", "--events", "30", "--procs", "1",
                     "--probe-events", "40", "--probe-rate", "6000", "--slot-mode", "replica")
     _check(out, 2, 2, 1, 30)
     assert out["config"]["cluster"] == "per-rank"
@@ -258,7 +288,7 @@ def test_bench_node_mode_four_slots_one_replica_one_monitor():
     on rank 0 supervise every GPU slot of the node (the production shape: one HA
     supervisor, one node agent); each rank is a slot whose runs sit on its GPU.  Every
     slot's HBM-OOM at about the same moment is attributed to that slot's physical GPU."""
-    out = _torchrun(4, "--steps", "2", "--warmup", "1", "--jobs", "200", "--events", "30", "--procs", "1",
+    out = _torchrun(4, "--full", "--steps", "2", "--warmup", "1", "--jobs", "200", "--events", "30", "--procs", "1",
                     "--probe-events", "10", "--probe-rate", "6000")
     _check(out, 4, 2, 1, 30)
     cfg = out["config"]

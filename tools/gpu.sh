@@ -11,7 +11,7 @@
 #   topo                  CPU / NUMA / cgroup layout and the GPU's PCI locality (gpurun_out/topo.log)
 #   tests[=EXPR]          pytest -m gpu (optionally -k EXPR), per-test 120 s timeout
 #   smoke                 __graft_entry__.smoke()
-#   bench[=ARGS]          python bench.py --steps ${BENCH_STEPS:-30} --warmup 2 ARGS
+#   bench[=ARGS]          python bench.py --full --steps ${BENCH_STEPS:-30} --warmup 2 ARGS
 #                         (ARGS: commas become spaces, e.g. bench=--procs,6)
 #   variant=NAME:ARGS     one bench logged as gpurun_out/var_NAME.log (A/B runs)
 #   repeat=N[:ARGS]       N benches in a row (median spread)
@@ -26,12 +26,14 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+LOGS=$(cd "$_" && pwd)  # the directory just made
 STEPS_N=${BENCH_STEPS:-30}
 summary=()
 
 run_bench() {  # name, timeout, extra args...
   local name=$1 t=$2; shift 2
-  timeout -k 10 "$t" python bench.py --steps "$STEPS_N" --warmup 2 "$@" > "gpurun_out/$name.log" 2> "gpurun_out/$name.err"
+  # --full: the summaries and A/B runs read the probe and the read-back, not only the headline figure
+  timeout -k 10 "$t" python bench.py --full --steps "$STEPS_N" --warmup 2 "$@" > "$LOGS/$name.log" 2> "$LOGS/$name.err"
   local rc=$?
   summary+=("$name: $(tail -1 "gpurun_out/$name.log" | cut -c1-240)")
   return $rc
