@@ -9,6 +9,8 @@
 ``shadow-report`` how a dry-run (shadow) supervisor's decisions agree with the checkpoint store
 ``build``       build the native components in-tree
 ``cqlsrv``      run the native in-memory CQL server (tests / local runs)
+``gpu-check``   ask one GPU whether it is bad: known-answer MFMA GEMM + HBM pattern test
+                (``--device D``, ``--quick``, ``--json``; exit 1 when a check fails)
 ``version``     print the version
 """
 from __future__ import annotations
@@ -70,6 +72,20 @@ def main(argv=None) -> int:
 
         # child process (never exec): keeps signal handling simple for callers
         return subprocess.call([binary("nexus-cqlsrv")] + argv)
+    if cmd == "gpu-check":
+        import argparse
+
+        from .gpu.health import check_gpu, summarize
+
+        ap = argparse.ArgumentParser(prog="nexus_supervisor_amd gpu-check")
+        ap.add_argument("--device", type=int, default=0)
+        ap.add_argument("--quick", action="store_true", help="1024^3 GEMM, one pass, 256 MiB of HBM")
+        ap.add_argument("--json", action="store_true", help="print the whole record")
+        a = ap.parse_args(argv)
+        quick = {"gemm": (1024, 1024, 1024), "seconds": 0.0, "hbm_mib": 256.0} if a.quick else {}
+        result = check_gpu(a.device, **quick)
+        print(json.dumps(result) if a.json else summarize(result))
+        return 0 if result["ok"] else 1
     if cmd == "version":
         from .buildmeta import main as version
 

@@ -9,6 +9,7 @@ artefact               sources                                 toolchain
 ``bin/nexus-cqlsrv``   ``csrc/cqlsrv/*.cpp`` (+ proto)         g++ (epoll)
 ``bin/nexus-kubesim``  ``csrc/kubesim/*.cpp`` (+ json.hpp)     g++ (epoll)
 ``bin/gpu_stress``     ``csrc/stress/gpu_stress.hip``          hipcc gfx950
+``bin/gpu_check``      ``csrc/health/gpu_check.hip``           hipcc gfx950
 ``_amdsmi_monitor_stub`` monitor over ``amdsmi_stub.cpp``      g++ (CPU tests)
 ``bin/monitor_selftest`` monitor threads over the stub          g++ (TSan/ASan)
 ``_certgen``           ``csrc/certgen/certgen.cpp``            g++ + libcrypto
@@ -148,6 +149,15 @@ def targets(sanitize: Optional[str] = None, out_root: Optional[str] = None) -> D
                                       "-Wall", "-Werror", *srcs, "-o", out],
             "requires": os.path.join(ROCM, "bin", "hipcc"),
         },
+        # the active device check (gpu/health.py): known-answer MFMA GEMM + HBM pattern test
+        "gpu_check": {
+            "out": os.path.join(bin_dir, "gpu_check"),
+            "srcs": [os.path.join(CSRC, "health", "gpu_check.hip")],
+            "deps": [],
+            "cmd": lambda out, srcs: [os.path.join(ROCM, "bin", "hipcc"), f"--offload-arch={ARCH}", "-O3", "-std=c++17",
+                                      "-Wall", "-Werror", *srcs, "-o", out],
+            "requires": os.path.join(ROCM, "bin", "hipcc"),
+        },
     }
 
 
@@ -265,7 +275,7 @@ def binary(name: str) -> str:
     """Path of a built helper binary, building it on demand."""
     ts = targets()
     key = {"nexus-cqlsrv": "cqlsrv", "gpu_stress": "gpu_stress", "nexus-kubesim": "kubesim",
-           "monitor_selftest": "monitor_selftest"}[name]
+           "monitor_selftest": "monitor_selftest", "gpu_check": "gpu_check"}[name]
     t = ts[key]
     if _stale(t):
         build_one(key, t)
