@@ -59,6 +59,10 @@ STAGE_FOR_ACTION = {
 _GPU_CLASSES = frozenset((F.HBM_OOM, F.GPU_FAULT, F.COLLECTIVE, F.GPU_ADMISSION))
 # Job event / condition reasons that imply one of the Job's pods has already failed
 _POD_FAILED_REASONS = frozenset(("BackoffLimitExceeded", "PodFailurePolicy"))
+# What a store step of supervise_action answers, as (code, value): the row was written; it
+# was not, and value is its current stage (None: no row); the decision is made, and value is
+# it; the conditional write cannot decide this row (the read + write step does).
+_WRITTEN, _NOT_WRITTEN, _DECIDED, _FALL_BACK = range(4)
 
 
 def _pod_failed(pod) -> bool:
@@ -279,7 +283,6 @@ class Supervisor:
         self.active_until = float("inf")
         self._label_check_at = 0.0
         self.label_mismatch = False
-        self._unfinished_cache: Optional[Tuple[str, ...]] = None
         self.gc_tuner = GcTuner.from_config(cfg.runtime, self.metrics)
         # replica shards owned right now (sharding.*), with a fencing epoch per shard
         self.shards = ShardSet.from_config(cfg)
@@ -1053,21 +1056,19 @@ class Supervisor:
 
     async def supervise_action(self, r: RunStatusAnalysisResult) -> Decision:
         """Reference ``superviseAction`` (``supervisor.go:261-374``) with the fixes of SURVEY §7.5."""
-        wall = self.wall
-        compat = self.cfg.compat
         r.attempts += 1
-        stamps = r.stamps
-        if stamps is not None and "dequeue" not in stamps:
-            stamps["dequeue"] = wall()
+        if "dequeue" not in r.stamps:
+            r.stamps["dequeue"] = self.wall()
         failing = r.action in A.FAILING
+        running = r.action == A.TO_RUNNING
         rid = r.request_id
+        key = (r.algorithm, rid)
         epoch = self._token(rid)
         if r.action not in STAGE_FOR_ACTION:
             raise ValueError(f"unknown analysis result action: {r.action}")
         if self._fenced(epoch, rid):
-            self.metrics.inc("decisions_fenced")
-            return Decision(r, "fenced", None, False)
-        applied = self._applied.get((r.algorithm, rid))
+            return self._fenced_decision(r)
+        applied = self._applied.get(key)
         if applied is not None and not r.pending_delete:
             # queued behind the decision that wrote this row (a run's Started Event and its
             # pod's Running transition; a pod's OOM and its Job's PodFailurePolicy): its stage
@@ -1075,7 +1076,7 @@ class Supervisor:
             if applied in _cp.FINISHED_STAGES:
                 self.metrics.inc("decisions_suppressed")
                 return await self._skip_finished(r, epoch, failing, applied)
-            if r.action == A.TO_RUNNING and applied == LifecycleStage.RUNNING:
+            if running and applied == LifecycleStage.RUNNING:
                 self.metrics.inc("decisions_suppressed")
                 return Decision(r, "skipped-already-running", applied, False)
         if failing and r.object_kind == "Job" and r.reason in _POD_FAILED_REASONS and self._settle_wait > 0:
@@ -1089,93 +1090,71 @@ class Supervisor:
             if self._log_fetches and r.object_kind == "Job":
                 await self._await_pod_logs(r)
             self.classifier.finish(r, self.lookup)
-        if self._fused or (self._fused_running and not failing):
-            d = await self._fused_action(r, epoch, failing)
-            if d is not None:
-                return d
-        try:
-            # the owned-columns write needs only the stage; the full-row upsert (reference
-            # UpsertCheckpoint of the deep copy) needs every column
-            pre = self._take_prefetch((r.algorithm, r.request_id)) if self._prefetch else None
-            if pre is not None:
-                cp = await pre  # started while the failure waited for its log tail / evidence
-                self.metrics.inc("checkpoint_reads_prefetch_used")
-            else:
-                read = self.store.read_checkpoint if compat.full_row_upsert else self.store.read_status
-                cp = await read(r.algorithm, r.request_id)
-            r.answered = r.attempts
-        except Exception as exc:
-            self.log.error(exc, "no checkpoint exists for the provided request, job will be deleted without metadata saved",
-                           requestId=r.request_id, algorithm=r.algorithm)
-            if compat.delete_on_read_error and failing:
-                try:
-                    await self._delete_job(r.request_id)
-                except Exception as del_exc:  # noqa: BLE001 - the read error is what is retried
-                    self.log.error(del_exc, "failed to delete an algorithm submission after a checkpoint read error",
-                                   requestId=r.request_id, algorithm=r.algorithm)
-            raise
-        stamps["read"] = wall()
-        key = (r.algorithm, r.request_id)
-        if cp is None:
-            return await self._skip_missing(r, failing)
-        if cp.is_finished():
-            return await self._skip_finished(r, epoch, failing, cp.lifecycle_stage)
+        # what is written, once for either store step (a known action is ToRunning or failing)
         stage = STAGE_FOR_ACTION[r.action]()
-        now_dt = _dt.datetime.fromtimestamp(wall(), _dt.timezone.utc)
-        if r.action == A.TO_RUNNING:
-            if cp.lifecycle_stage == LifecycleStage.RUNNING and not compat.full_row_upsert:
-                self._remember(key, stage)
-                return Decision(r, "skipped-already-running", stage, False)
-            if self._fenced(epoch, rid):
-                self.metrics.inc("decisions_fenced")
-                return Decision(r, "fenced", None, False)
-            if not await self._write(cp, stage, None, None, now_dt, set_failure=False, running=True):
-                return await self._lost_race(r, key)
-            stamps["ack"] = wall()
-            stamps["ack_mono"] = time.monotonic()
-            self._observe(r)
-            self._remember(key, stage)
-            return Decision(r, "applied", stage, False)
-        cause = R.failure_cause(r.action, r.run_status_message, compat.doubled_fatal_cause)
-        details = render_trace(r, self.cfg.rules.trace_format, self.cfg.rules.trace_max_bytes)
+        cause = details = None
+        if failing:
+            cause = R.failure_cause(r.action, r.run_status_message, self.cfg.compat.doubled_fatal_cause)
+            details = render_trace(r, self.cfg.rules.trace_format, self.cfg.rules.trace_max_bytes)
+        # the store step, the one part that differs: one conditional write, or read + write
+        code, current = _FALL_BACK, None
+        if self._fused or (self._fused_running and not failing):
+            code, current = await self._cas_step(r, epoch, running, stage, cause, details)
+        if code == _FALL_BACK:
+            code, current = await self._read_write_step(r, epoch, running, key, stage, cause, details)
+        if code == _DECIDED:  # fenced right before the write, or a lost race's answer
+            return current
+        if code == _NOT_WRITTEN:
+            if current is None:
+                return await self._skip_missing(r, failing)
+            if current in _cp.FINISHED_STAGES:
+                return await self._skip_finished(r, epoch, failing, current)
+            # ToRunning on a RUNNING row: the only other stage a store step leaves unwritten
+            self._remember(key, current)
+            return Decision(r, "skipped-already-running", current, False)
         # The reference deletes the Job, then upserts the row (supervisor.go:289-301).  This
         # build writes first: deleting first (or concurrently) lets a crash between the two
         # lose the decision for good — the Job's pods are garbage-collected, so the replay
         # after failover has nothing to re-decide from.  Written-then-crashed instead leaves
         # a failed row whose Job still exists, which the replay finishes (finished path).
-        if self._fenced(epoch, rid):
-            self.metrics.inc("decisions_fenced")
-            return Decision(r, "fenced", None, False)
+        d = self._after_write(r, epoch, key, stage, running)
+        if d is not None:
+            return d
         try:
-            written = await self._write(cp, stage, cause, details, now_dt, set_failure=True)
+            deleted = await self._delete_job(rid)
         except Exception as exc:
-            self.log.error(exc, "failed to update algorithm submission status", requestId=r.request_id, algorithm=r.algorithm)
+            self.log.error(exc, "failed to delete an algorithm submission", requestId=rid, algorithm=r.algorithm)
+            r.pending_delete = True  # the retry sees the finished row and only deletes
             raise
-        if not written:
-            return await self._lost_race(r, key)
-        stamps["ack"] = wall()
+        return Decision(r, "applied", stage, deleted)
+
+    def _fenced_decision(self, r: RunStatusAnalysisResult) -> Decision:
+        self.metrics.inc("decisions_fenced")
+        return Decision(r, "fenced", None, False)
+
+    def _after_write(self, r: RunStatusAnalysisResult, epoch, key, stage: str, running: bool) -> Optional[Decision]:
+        """What follows a durable write, whichever store step made it.  None when the Job
+        DELETE is synchronous (``async-job-delete`` off): the caller awaits it."""
+        stamps = r.stamps
+        stamps["ack"] = self.wall()
         stamps["ack_mono"] = time.monotonic()
         self._observe(r)
         self._remember(key, stage)
+        if running:
+            return Decision(r, "applied", stage, False)
         self.metrics.inc("decisions_applied", labels={"stage": stage, "class": r.failure_class or "none"})
         if r.failure_class in _GPU_CLASSES:
             self._count_gpu_failure(r)
         if self.cfg.observability.record_events and not self.cfg.dry_run:
             self._record_event(r, stage)
-        if self._fenced(epoch, rid):  # durable, but the Job now belongs to the new leader's replay
+        if self._fenced(epoch, r.request_id):  # durable, but the Job now belongs to the new leader's replay
             return Decision(r, "applied", stage, False)
         if self.cfg.async_job_delete:
             # the decision is durable; the Job DELETE must not hold a worker (and with it
             # every later decision) hostage to API-server latency
             self._spawn_delete(r)
             return Decision(r, "applied", stage, False)
-        try:
-            deleted = await self._delete_job(r.request_id)
-        except Exception as exc:
-            self.log.error(exc, "failed to delete an algorithm submission", requestId=r.request_id, algorithm=r.algorithm)
-            r.pending_delete = True  # the retry sees the finished row and only deletes
-            raise
-        return Decision(r, "applied", stage, deleted)
+        return None
 
     async def _await_pod_failure(self, r: RunStatusAnalysisResult) -> None:
         """A Job's BackoffLimitExceeded / PodFailurePolicy means a pod of it failed.  When
@@ -1286,7 +1265,55 @@ class Supervisor:
         self.metrics.inc("decisions_skipped_finished")
         return Decision(r, "skipped-finished", current, deleted)
 
-    async def _fused_action(self, r: RunStatusAnalysisResult, epoch, failing: bool) -> Optional[Decision]:
+    async def _read_write_step(self, r: RunStatusAnalysisResult, epoch, running: bool, key, stage, cause,
+                               details) -> Tuple[int, Any]:
+        """The reference's store step (``supervisor.go:264-301``): read the row (or take the
+        read prefetched while the failure waited), then write."""
+        compat = self.cfg.compat
+        failing = not running
+        try:
+            # the owned-columns write needs only the stage; the full-row upsert (reference
+            # UpsertCheckpoint of the deep copy) needs every column
+            pre = self._take_prefetch(key) if self._prefetch else None
+            if pre is not None:
+                cp = await pre  # started while the failure waited for its log tail / evidence
+                self.metrics.inc("checkpoint_reads_prefetch_used")
+            else:
+                read = self.store.read_checkpoint if compat.full_row_upsert else self.store.read_status
+                cp = await read(r.algorithm, r.request_id)
+            r.answered = r.attempts
+        except Exception as exc:
+            self.log.error(exc, "no checkpoint exists for the provided request, job will be deleted without metadata saved",
+                           requestId=r.request_id, algorithm=r.algorithm)
+            if compat.delete_on_read_error and failing:
+                try:
+                    await self._delete_job(r.request_id)
+                except Exception as del_exc:  # noqa: BLE001 - the read error is what is retried
+                    self.log.error(del_exc, "failed to delete an algorithm submission after a checkpoint read error",
+                                   requestId=r.request_id, algorithm=r.algorithm)
+            raise
+        r.stamps["read"] = self.wall()
+        if cp is None:
+            return _NOT_WRITTEN, None
+        if cp.is_finished():
+            return _NOT_WRITTEN, cp.lifecycle_stage
+        now_dt = _dt.datetime.fromtimestamp(self.wall(), _dt.timezone.utc)
+        if running and cp.lifecycle_stage == LifecycleStage.RUNNING and not compat.full_row_upsert:
+            return _NOT_WRITTEN, cp.lifecycle_stage
+        if self._fenced(epoch, r.request_id):
+            return _DECIDED, self._fenced_decision(r)
+        try:
+            written = await self._write(cp, stage, cause, details, now_dt, set_failure=failing, running=running)
+        except Exception as exc:
+            if failing:
+                self.log.error(exc, "failed to update algorithm submission status", requestId=r.request_id,
+                               algorithm=r.algorithm)
+            raise
+        if not written:
+            return _DECIDED, await self._lost_race(r, key)
+        return _WRITTEN, None
+
+    async def _cas_step(self, r: RunStatusAnalysisResult, epoch, running: bool, stage, cause, details) -> Tuple[int, Any]:
         """``compat.fused-write``: the decision is ONE conditional write
         (``UPDATE … IF lifecycle_stage IN (<unfinished stages>)``) instead of the reference's
         read followed by a write (``supervisor.go:264-301``).  The store checks the stage
@@ -1299,30 +1326,20 @@ class Supervisor:
         not-applied answer carries the row's stage, which drives the reference's skip paths
         (no row / finished / ToRunning on a RUNNING row).  The price is a Paxos round (~4
         replica round trips, serialised per partition; ``compat.fused-write: auto`` uses it
-        only under HA — docs/ARCHITECTURE.md "Pricing the LWT").  Returns None for a stage
-        outside the known set (custom stage strings): the two-step path then decides with
+        only under HA — docs/ARCHITECTURE.md "Pricing the LWT").  Falls back for a stage
+        outside the known set (custom stage strings): the two-step step then decides with
         that stage in its guard."""
-        wall = self.wall
-        compat = self.cfg.compat
-        stamps = r.stamps
         rid = r.request_id
-        stage = STAGE_FOR_ACTION[r.action]()
-        running = r.action == A.TO_RUNNING
+        failing = not running
         only_if = self._unfinished_guard(running)
-        if running:
-            cause = details = None
-        else:
-            cause = R.failure_cause(r.action, r.run_status_message, compat.doubled_fatal_cause)
-            details = render_trace(r, self.cfg.rules.trace_format, self.cfg.rules.trace_max_bytes)
         if self._fenced(epoch, rid):
-            self.metrics.inc("decisions_fenced")
-            return Decision(r, "fenced", None, False)
-        t = wall()
-        stamps["prepare"] = t  # no read in this path: dequeue → here is local work, here → ack the CAS
+            return _DECIDED, self._fenced_decision(r)
+        t = self.wall()
+        r.stamps["prepare"] = t  # no read in this path: dequeue → here is local work, here → ack the CAS
         now_dt = _dt.datetime.fromtimestamp(t, _dt.timezone.utc)
         try:
             applied, current = await self.store.cas_update(r.algorithm, rid, stage, cause, details, now_dt,
-                                                           only_if, set_failure=not running)
+                                                           only_if, set_failure=failing)
             r.answered = r.attempts
         except Exception as exc:
             self.log.error(exc, "failed to update algorithm submission status", requestId=rid, algorithm=r.algorithm)
@@ -1330,49 +1347,22 @@ class Supervisor:
             # the one store call is the write itself, so delete only when it provably never
             # reached the store — a timed-out write may have landed, and deleting then could
             # leave an unfinished row with nothing left to replay from
-            if compat.delete_on_read_error and failing and isinstance(exc, NotSent):
+            if self.cfg.compat.delete_on_read_error and failing and isinstance(exc, NotSent):
                 try:
                     await self._delete_job(rid)
                 except Exception as del_exc:  # noqa: BLE001 - the store error is what is retried
                     self.log.error(del_exc, "failed to delete an algorithm submission after a checkpoint store error",
                                    requestId=rid, algorithm=r.algorithm)
             raise
-        key = (r.algorithm, rid)
-        if not applied:
-            if current is not None:
-                self.metrics.inc("conditional_write_rejected")
-            if current is None:
-                return await self._skip_missing(r, failing)
-            if current in _cp.FINISHED_STAGES:
-                return await self._skip_finished(r, epoch, failing, current)
-            if running and current == LifecycleStage.RUNNING:
-                self._remember(key, current)
-                return Decision(r, "skipped-already-running", current, False)
-            self.metrics.inc("fused_write_fallbacks")
-            return None
-        stamps["ack"] = wall()
-        stamps["ack_mono"] = time.monotonic()
-        self._observe(r)
-        self._remember(key, stage)
-        if running:
-            return Decision(r, "applied", stage, False)
-        self.metrics.inc("decisions_applied", labels={"stage": stage, "class": r.failure_class or "none"})
-        if r.failure_class in _GPU_CLASSES:
-            self._count_gpu_failure(r)
-        if self.cfg.observability.record_events and not self.cfg.dry_run:
-            self._record_event(r, stage)
-        if self._fenced(epoch, rid):
-            return Decision(r, "applied", stage, False)
-        if self.cfg.async_job_delete:
-            self._spawn_delete(r)
-            return Decision(r, "applied", stage, False)
-        try:
-            deleted = await self._delete_job(rid)
-        except Exception as exc:
-            self.log.error(exc, "failed to delete an algorithm submission", requestId=rid, algorithm=r.algorithm)
-            r.pending_delete = True  # the retry sees the finished row and only deletes
-            raise
-        return Decision(r, "applied", stage, deleted)
+        if applied:
+            return _WRITTEN, None
+        if current is None:
+            return _NOT_WRITTEN, None
+        self.metrics.inc("conditional_write_rejected")
+        if current in _cp.FINISHED_STAGES or (running and current == LifecycleStage.RUNNING):
+            return _NOT_WRITTEN, current
+        self.metrics.inc("fused_write_fallbacks")
+        return _FALL_BACK, None
 
     def _unfinished_guard(self, running: bool) -> Tuple[str, ...]:
         """``IF lifecycle_stage IN (...)`` of a fused write, memoised per stage configuration
@@ -1399,12 +1389,20 @@ class Supervisor:
                 self._deletes[fut] = r.request_id
                 fut.add_done_callback(lambda f, r=r: self._delete_settled(r, f))
                 return
-        t = asyncio.ensure_future(self._delete_with_retry(r))
+        self._start_delete_retry(r)
+
+    def _start_delete_retry(self, r: RunStatusAnalysisResult, first_delay: float = 0.0) -> None:
+        t = asyncio.ensure_future(self._delete_with_retry(r, first_delay=first_delay))
         self._deletes[t] = r.request_id
         t.add_done_callback(self._delete_done)
 
     def _delete_done(self, t) -> None:
         self._deletes.pop(t, None)
+
+    def _observe_delete(self, r: RunStatusAnalysisResult) -> None:
+        ack = r.stamps.get("ack")
+        if ack is not None:
+            self.metrics.observe_seconds("stage_delete", self.wall() - ack)
 
     def _delete_settled(self, r: RunStatusAnalysisResult, fut) -> None:
         self._deletes.pop(fut, None)
@@ -1422,18 +1420,14 @@ class Supervisor:
                 exc = e
         if exc is None:
             self.metrics.inc("jobs_deleted")
-            ack = r.stamps.get("ack") if r.stamps else None
-            if ack is not None:
-                self.metrics.observe_seconds("stage_delete", self.wall() - ack)
+            self._observe_delete(r)
             return
         if not self.active or not self.shards.owns(r.request_id):
             return  # fenced: the new leader's (shard owner's) replay owns this Job
         self.metrics.inc("job_delete_retries")
         # a throttled DELETE (429) waits at least for the server's Retry-After hint
         first = max(self.cfg.failure_rate_base_delay, getattr(exc, "retry_after", None) or 0.0)
-        t = asyncio.ensure_future(self._delete_with_retry(r, first_delay=first))
-        self._deletes[t] = r.request_id
-        t.add_done_callback(self._delete_done)
+        self._start_delete_retry(r, first)
 
     async def _delete_with_retry(self, r: RunStatusAnalysisResult, first_delay: float = 0.0) -> None:
         """Background Job DELETE after a durable failure write.  The key is already marked
@@ -1460,9 +1454,7 @@ class Supervisor:
             attempt += 1
             try:
                 await self._delete_job(r.request_id)
-                ack = r.stamps.get("ack") if r.stamps else None
-                if ack is not None:
-                    self.metrics.observe_seconds("stage_delete", self.wall() - ack)
+                self._observe_delete(r)
                 return
             except asyncio.CancelledError:
                 raise
