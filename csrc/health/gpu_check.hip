@@ -1,6 +1,7 @@
 // gpu_check — an active device check with exact answers: "is this GPU bad, or was it the job?"
 //
-//   gpu_check gemm --m M --n N --k K [--seed S] [--a FILE --b FILE] [--c-out FILE]
+//   gpu_check gemm [--dtype bf16|mxfp8|mxfp4] --m M --n N --k K [--seed S]
+//                  [--a FILE --b FILE [--sa FILE --sb FILE]] [--c-out FILE]
 //                  [--poison I,J] [--device D] [--seconds T]
 //        bf16 x bf16 -> fp32 GEMM on the matrix units (v_mfma_f32_32x32x16_bf16), checked on
 //        the device by Huang-Abraham checksums.  Every element of A (M x K, row-major) and
@@ -9,6 +10,19 @@
 //        any summation order: a healthy device agrees bit for bit with integer arithmetic and
 //        the comparison is ==, no tolerance.  The expected checksums come from integer kernels
 //        that share nothing with the matrix path.
+//        --dtype mxfp8 / mxfp4: the same check in the OCP microscaling formats on the scaled
+//        matrix path (v_mfma_scale_f32_32x32x64_f8f6f4): E4M3 or E2M1 elements with one E8M0
+//        scale per 32 consecutive k, SA[M][K/32] and SB[N][K/32], each 127 or 128 (x1 or x2)
+//        and varying per (row, block).
+//          mxfp8: elements are integers in [-2, 2] (bytes 00 38 40 B8 C0), so a scaled product
+//          is an integer of magnitude <= (2*2)*(2*2) = 16 and a checksum over 128 rows of K
+//          products is at most 16*K*128 <= 2^24 for K <= 8192.
+//          mxfp4: elements are in {0, +-0.5, +-1, +-1.5, +-2} (codes 0..4, sign in bit 3; two
+//          per byte, even k in the low nibble), so a scaled product is a multiple of 1/4 of
+//          magnitude <= 16 = 64 quarter-units and 64*K*128 <= 2^24 for K <= 2048.
+//        Within those caps fp32 is again exact in any order and the comparison stays ==; the
+//        expected checksums are integers in units of 1 (mxfp8) or 1/4 (mxfp4).  --a/--b are
+//        raw element bytes (M*K, N*K; for mxfp4 half that), --sa/--sb the scale bytes.
 //   gpu_check hbm --mib SIZE [--passes P] [--seed S] [--flip WORD:MASK] [--device D]
 //        moving inversions over one allocation: pass 0 writes an address hash, each later pass
 //        loads, compares with what the pass before wrote and stores the next pattern (odd
@@ -79,6 +93,46 @@ __global__ __launch_bounds__(256) void generate_kernel(uint16_t* __restrict__ x,
   }
 }
 
+// The microscaling inputs, from the same hash.  X is rows x K elements; one thread writes 16
+// bytes: 16 E4M3 bytes, or 32 E2M1 nibbles (one whole scale block).  K is a multiple of 64.
+enum Fmt { BF16 = 0, MXFP8 = 1, MXFP4 = 2 };
+
+template <int FMT>
+__device__ static inline uint32_t small_mx_code(uint32_t seed, uint32_t row, uint32_t col) {
+  const uint32_t h = mix32(mix32(seed ^ (row * 0x9e3779b9u)) + col);
+  if (FMT == MXFP8) {  // -2 .. 2
+    const int v = static_cast<int>(h % 5u) - 2;
+    return v == 0 ? 0u : ((v < 0 ? 0x80u : 0u) | ((v == 2 || v == -2) ? 0x40u : 0x38u));
+  }
+  const int v = static_cast<int>(h % 9u) - 4;  // half-units -4 .. 4: the code is the magnitude
+  return v < 0 ? 8u | static_cast<uint32_t>(-v) : static_cast<uint32_t>(v);
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void generate_mx_kernel(unsigned char* __restrict__ x, int rows, int K, uint32_t seed) {
+  constexpr int PER = FMT == MXFP8 ? 16 : 32;  // elements per 16-byte chunk
+  const size_t chunks = static_cast<size_t>(rows) * (K / PER);
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t c = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; c < chunks; c += stride) {
+    const uint32_t row = static_cast<uint32_t>(c / (K / PER)), col = static_cast<uint32_t>(c % (K / PER)) * PER;
+    u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int e = 0; e < PER; ++e)  // element e sits at bit e * (128 / PER) of the chunk
+      v[e / (PER / 4)] |= small_mx_code<FMT>(seed, row, col + e) << (e % (PER / 4) * (128 / PER));
+    *reinterpret_cast<u32x4*>(x + c * 16) = v;
+  }
+}
+
+// S is rows x K/32 E8M0 bytes, each 127 or 128; salted so that it is no function of the elements
+__global__ __launch_bounds__(256) void generate_scale_kernel(unsigned char* __restrict__ s, int rows, int KS, uint32_t seed) {
+  const size_t n = static_cast<size_t>(rows) * KS;
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t x = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; x < n; x += stride) {
+    const uint32_t row = static_cast<uint32_t>(x / KS), blk = static_cast<uint32_t>(x % KS);
+    s[x] = 127u + (mix32(mix32(~seed ^ (row * 0x9e3779b9u)) + blk) >> 31);
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // The GEMM with checksum epilogue
 // ------------------------------------------------------------------------------------------
@@ -87,6 +141,74 @@ constexpr int TILE = 128;                  // C tile edge per workgroup
 constexpr int KSTEP = 64;                  // K advance per LDS stage
 constexpr int ROW_BYTES = KSTEP * 2 + 16;  // 128 B of data + 16 B pad
 constexpr int STAGE_BYTES = TILE * ROW_BYTES;
+
+// The checksum epilogue of both GEMM kernels, from registers: the 128x128 tile is held as 2x2
+// blocks of 32x32 accumulators per wave, register r of lane l holding
+// D[8 * (r / 4) + 4 * (l / 32) + r % 4][l % 32].  `red` is 512 floats of LDS that no wave reads
+// any more.  Element (bm, bn, r) of this lane is
+//   row  row0 + wm*64 + bm*32 + 8*(r/4) + 4*half + r%4,   column  col0 + wn*64 + bn*32 + l32.
+__device__ __forceinline__ void abft_epilogue(f32x16 (&acc)[2][2], float* red, int M, int N, float* __restrict__ colsum,
+                                              float* __restrict__ rowsum, float* __restrict__ C, int poison_i,
+                                              int poison_j) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w >> 1, wn = w & 1;
+  const int l32 = lane & 31, half = lane >> 5;
+  const int tn = blockIdx.x, tm = blockIdx.y;
+  const int row0 = tm * TILE, col0 = tn * TILE;
+  const int lane_row = row0 + wm * 64 + 4 * half, lane_col = col0 + wn * 64 + l32;
+  if (poison_i >= 0) {  // detector self-test: one element off by one
+#pragma unroll
+    for (int bm = 0; bm < 2; ++bm)
+#pragma unroll
+      for (int bn = 0; bn < 2; ++bn)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const bool hit = lane_row + bm * 32 + 8 * (r >> 2) + (r & 3) == poison_i && lane_col + bn * 32 == poison_j;
+          acc[bm][bn][r] += hit ? 1.0f : 0.0f;
+        }
+  }
+
+  // red [0,256): column partials by wm; [256,512): row partials by wn
+  // column sums: over this lane's 32 registers, then across the two half-waves
+#pragma unroll
+  for (int bn = 0; bn < 2; ++bn) {
+    float cs = 0.0f;
+#pragma unroll
+    for (int bm = 0; bm < 2; ++bm)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) cs += acc[bm][bn][r];
+    cs += __shfl_xor(cs, 32);
+    if (half == 0) red[wm * TILE + wn * 64 + bn * 32 + l32] = cs;
+  }
+  // row sums: per register over both column blocks, then a butterfly over the 32 lanes of a half-wave
+#pragma unroll
+  for (int bm = 0; bm < 2; ++bm)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float rs = acc[bm][0][r] + acc[bm][1][r];
+#pragma unroll
+      for (int off = 16; off >= 1; off >>= 1) rs += __shfl_xor(rs, off);
+      if (l32 == 0) red[2 * TILE + wn * TILE + wm * 64 + bm * 32 + 8 * (r >> 2) + 4 * half + (r & 3)] = rs;
+    }
+  __syncthreads();
+  if (t < TILE) {
+    if (col0 + t < N) colsum[static_cast<size_t>(tm) * N + col0 + t] = red[t] + red[TILE + t];
+  } else {
+    const int u = t - TILE;
+    if (row0 + u < M) rowsum[static_cast<size_t>(tn) * M + row0 + u] = red[2 * TILE + u] + red[3 * TILE + u];
+  }
+
+  if (C != nullptr) {  // --c-out only; the production run never stores M x N
+#pragma unroll
+    for (int bm = 0; bm < 2; ++bm)
+#pragma unroll
+      for (int bn = 0; bn < 2; ++bn)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = lane_row + bm * 32 + 8 * (r >> 2) + (r & 3), col = lane_col + bn * 32;
+          if (row < M && col < N) C[static_cast<size_t>(row) * N + col] = acc[bm][bn][r];
+        }
+  }
+}
 
 // Compiled for gfx950 (-O3, kernel-resource-usage): 112 VGPRs + 64 AGPRs (the accumulators),
 // 73728 B LDS, 0 scratch, 0 SGPR/VGPR spills; occupancy 2 waves per SIMD (two workgroups per
@@ -181,62 +303,205 @@ __global__ __launch_bounds__(256) void gemm_abft_kernel(const uint16_t* __restri
 #undef LOAD_GLOBAL
 #undef STORE_LDS
 
-  // Epilogue, from registers.  Element (bm, bn, r) of this lane is
-  //   row  row0 + wm*64 + bm*32 + 8*(r/4) + 4*half + r%4,   column  col0 + wn*64 + bn*32 + l32.
-  const int lane_row = row0 + wm * 64 + 4 * half, lane_col = col0 + wn * 64 + l32;
-  if (poison_i >= 0) {  // detector self-test: one element off by one
-#pragma unroll
-    for (int bm = 0; bm < 2; ++bm)
-#pragma unroll
-      for (int bn = 0; bn < 2; ++bn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const bool hit = lane_row + bm * 32 + 8 * (r >> 2) + (r & 3) == poison_i && lane_col + bn * 32 == poison_j;
-          acc[bm][bn][r] += hit ? 1.0f : 0.0f;
-        }
-  }
+  abft_epilogue(acc, reinterpret_cast<float*>(lds), M, N, colsum, rowsum, C, poison_i, poison_j);
+}
 
-  float* red = reinterpret_cast<float*>(lds);  // [0,256): column partials by wm; [256,512): row partials by wn
-  // column sums: over this lane's 32 registers, then across the two half-waves
-#pragma unroll
-  for (int bn = 0; bn < 2; ++bn) {
-    float cs = 0.0f;
-#pragma unroll
-    for (int bm = 0; bm < 2; ++bm)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) cs += acc[bm][bn][r];
-    cs += __shfl_xor(cs, 32);
-    if (half == 0) red[wm * TILE + wn * 64 + bn * 32 + l32] = cs;
+// ------------------------------------------------------------------------------------------
+// The microscaling GEMM (MXFP8, MXFP4) with the same checksum epilogue
+// ------------------------------------------------------------------------------------------
+
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+
+constexpr int MX_ROW_BYTES = 128;  // one stage row: 128 k of fp8 or 256 k of fp4, no padding
+constexpr int MX_STAGE_BYTES = TILE * MX_ROW_BYTES;
+
+// Four consecutive E8M0 bytes of one row of S (rows x KS) from block kb, a multiple of 4; 127
+// (x1.0) where there is no row or no block: those elements are zero-filled anyway.  K is a
+// multiple of 64, so KS is even: a row starts 2-byte aligned (4-byte when K is a multiple of
+// 128) and ends on a whole or a half word, and nothing outside the row is read.
+__device__ static inline uint32_t load_scale_word(const unsigned char* __restrict__ S, int row, int rows, int KS, int kb) {
+  uint32_t w = 0x7f7f7f7fu;
+  if (row < rows && kb < KS) {
+    const void* p = __builtin_assume_aligned(S + static_cast<size_t>(row) * KS + kb, 2);
+    if (kb + 4 <= KS) {
+      __builtin_memcpy(&w, p, 4);
+    } else {
+      uint16_t h;
+      __builtin_memcpy(&h, p, 2);
+      w = 0x7f7f0000u | h;
+    }
   }
-  // row sums: per register over both column blocks, then a butterfly over the 32 lanes of a half-wave
+  return w;
+}
+
+// The 64 k of one instruction for this wave's 2x2 blocks.  `pa`/`pb` are the lane's LDS rows,
+// `ch` its (swizzled) first 16-byte chunk; the scale words were shifted by 8 * half when loaded, so
+// that OPSEL (an immediate: byte 0 or 2) serves both half-waves.
+template <int FMT, int OPSEL>
+__device__ __forceinline__ void mx_mfma_2x2(const unsigned char* pa, const unsigned char* pb, int ch, uint32_t sa0,
+                                            uint32_t sa1, uint32_t sb0, uint32_t sb1, f32x16 (&acc)[2][2]) {
+  constexpr int CB = FMT == MXFP4 ? 4 : 0;  // cbsz / blgp: E4M3 or E2M1
+  const i32x4 a0l = *reinterpret_cast<const i32x4*>(pa + ch * 16);
+  const i32x4 a1l = *reinterpret_cast<const i32x4*>(pa + 32 * MX_ROW_BYTES + ch * 16);
+  const i32x4 b0l = *reinterpret_cast<const i32x4*>(pb + ch * 16);
+  const i32x4 b1l = *reinterpret_cast<const i32x4*>(pb + 32 * MX_ROW_BYTES + ch * 16);
+  i32x8 a0, a1, b0, b1;
+  if (FMT == MXFP8) {  // 32 bytes per lane: this chunk of the first block and the same of the second
+    const int c2 = (ch ^ 2) * 16;
+    a0 = __builtin_shufflevector(a0l, *reinterpret_cast<const i32x4*>(pa + c2), 0, 1, 2, 3, 4, 5, 6, 7);
+    a1 = __builtin_shufflevector(a1l, *reinterpret_cast<const i32x4*>(pa + 32 * MX_ROW_BYTES + c2), 0, 1, 2, 3, 4, 5, 6, 7);
+    b0 = __builtin_shufflevector(b0l, *reinterpret_cast<const i32x4*>(pb + c2), 0, 1, 2, 3, 4, 5, 6, 7);
+    b1 = __builtin_shufflevector(b1l, *reinterpret_cast<const i32x4*>(pb + 32 * MX_ROW_BYTES + c2), 0, 1, 2, 3, 4, 5, 6, 7);
+  } else {  // 16 bytes per lane; with cbsz/blgp 4 the upper four registers are not read
+    a0 = __builtin_shufflevector(a0l, a0l, 0, 1, 2, 3, -1, -1, -1, -1);
+    a1 = __builtin_shufflevector(a1l, a1l, 0, 1, 2, 3, -1, -1, -1, -1);
+    b0 = __builtin_shufflevector(b0l, b0l, 0, 1, 2, 3, -1, -1, -1, -1);
+    b1 = __builtin_shufflevector(b1l, b1l, 0, 1, 2, 3, -1, -1, -1, -1);
+  }
+  acc[0][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a0, b0, acc[0][0], CB, CB, OPSEL, sa0, OPSEL, sb0);
+  acc[0][1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a0, b1, acc[0][1], CB, CB, OPSEL, sa0, OPSEL, sb1);
+  acc[1][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a1, b0, acc[1][0], CB, CB, OPSEL, sa1, OPSEL, sb0);
+  acc[1][1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a1, b1, acc[1][1], CB, CB, OPSEL, sa1, OPSEL, sb1);
+}
+
+// Compiled for gfx950 (-O3, kernel-resource-usage):
+//   MXFP8: 152 VGPRs + 64 AGPRs (the accumulators), 65536 B LDS, 0 scratch, 0 SGPR/VGPR spills
+//   MXFP4: 162 VGPRs + 64 AGPRs, 65536 B LDS, 0 scratch, 0 SGPR/VGPR spills
+// both at occupancy 2 waves per SIMD: two workgroups per CU, bounded by LDS (2 x 64 KB of
+// 160 KB) and equally by registers (216 and 226 of 512 per SIMD lane).
+//
+// The work split is that of gemm_abft_kernel: one workgroup (4 waves) per 128x128 tile of C,
+// wave w the 64x64 quadrant (w / 2, w % 2) as 2x2 blocks, here of
+// v_mfma_scale_f32_32x32x64_f8f6f4; the epilogue is shared.  What differs is how the data moves.
+//
+// Operand layout of the instruction (CDNA4 ISA guide, matrix arithmetic; settled on the device
+// by the one-instruction shape of the tests): lane l supplies row (A) or column (B) l % 32, and
+// its scale register (one E8M0 byte of it, picked by OPSEL: the immediate is the byte index)
+// scales the MX block l / 32 of the 64 k, for every lane of that row.
+//   E2M1 (cbsz/blgp 4): four registers, the 32 consecutive k of block l / 32, lower k in the low
+//   nibble: one MX block is exactly one lane's operand.
+//   E4M3: eight registers, but *not* 32 consecutive k: registers 0..3 are the 16 k from
+//   16 * (l / 32) of block 0 and registers 4..7 the 16 k from 16 * (l / 32) of block 1.  Each
+//   half-wave holds half of both blocks, and a lane's scale also applies to the other
+//   half-wave's registers of that block.  (Fed as 32 consecutive k per lane the products are
+//   right and the scales are crossed: all-ones elements or all-equal scales do not show it.)
+// The accumulator layout is that of the other 32x32 instructions.
+//
+// LDS: per stage 128 rows x 128 bytes of A and of B (128 k of fp8 or 256 k of fp4: the
+// geometry is shared, only the k bookkeeping differs), two stages, 64 KB.  Rows are *not*
+// padded: a lane reads two 16-byte chunks 32 bytes apart (fp8, two ds_read_b128) or one (fp4)
+// per instruction, and the 16-byte chunk c of row r is stored at chunk c ^ key(r),
+//   key(r) = (r & 7) ^ ((r >> 3) & 1),
+// an xor swizzle.  With 64 banks of 4 bytes the bank group of a 16-byte access is
+// 8 * (r & 1) + (c ^ key(r)) of 16.  A ds_read_b128 serves 16 lanes together, rows r .. r+15
+// at one c (both formats: the half-wave offset and the MFMA index only change c): rows 0..7
+// have distinct keys whose low bit equals r & 1, rows 8..15 distinct keys whose low bit
+// differs from r & 1, so the sixteen (r & 1, key) pairs are distinct and the reads are
+// conflict-free.  Counted with 32 banks and 8 lanes together the group is c ^ key(r) of 8 and
+// rows r .. r+7 have 8 distinct keys: conflict-free as well.  The stage writes (8 lanes cover
+// the 8 chunks of a row, the next 8 lanes row r+1) fill one 128-byte half of the banks per
+// row and the other half for the next row: conflict-free too, where the padded bf16 layout
+// overlaps at the seam.  Against padding the swizzle costs one xor per read address and saves
+// 8 KB; the xor folds the half-wave offset into the per-lane term, so it is one VALU
+// operation per instruction and operand, next to a 16- or 8-pass MFMA.
+//
+// Scales do not go through LDS.  A K step is 4 (fp8) or 8 (fp4) blocks per row, one or two
+// 32-bit words of SA[M][K/32]; each lane loads the words of its own 2 + 2 rows with the next
+// stage's global loads.  The two half-waves supply blocks 2*kk and 2*kk + 1 of instruction kk
+// and OPSEL is an immediate, so the word is shifted right by 8 * half once when it is loaded
+// and OPSEL is 0 for even kk, 2 for odd kk.
+//
+// Rows past M, columns past N and bytes past the row are zero-filled in LDS, never read from
+// memory.  K is a multiple of 64 and a row starts 16-byte aligned, so a 16-byte chunk is
+// wholly inside or wholly outside.
+template <int FMT>
+__global__ __launch_bounds__(256) void gemm_abft_mx_kernel(const unsigned char* __restrict__ A,
+                                                           const unsigned char* __restrict__ B,
+                                                           const unsigned char* __restrict__ SA,
+                                                           const unsigned char* __restrict__ SB, int M, int N, int K,
+                                                           float* __restrict__ colsum, float* __restrict__ rowsum,
+                                                           float* __restrict__ C, int poison_i, int poison_j) {
+  constexpr bool FP4 = FMT == MXFP4;
+  constexpr int CPI = FP4 ? 1 : 2;  // 16-byte chunks per lane and instruction
+  constexpr int SW = FP4 ? 2 : 1;   // scale words per row and stage; 2 * SW instructions along k
+  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * MX_STAGE_BYTES];  // [stage][A, B]
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w >> 1, wn = w & 1;
+  const int l32 = lane & 31, half = lane >> 5;
+  const int row0 = blockIdx.y * TILE, col0 = blockIdx.x * TILE;
+  const int KB = FP4 ? K / 2 : K, KS = K / 32;  // bytes and scales per row
+
+  // global -> LDS copy as in the bf16 kernel: 4 chunks per thread per operand, rows lr + 32 q
+  // (all with the key of lr), 8 consecutive lanes per 128-byte row segment
+  const int lr = t >> 3, kc = t & 7;
+  const int wch = kc ^ (lr & 7) ^ ((lr >> 3) & 1);
+  u32x4 ga[4], gb[4];
+  uint32_t sa[2][SW], sb[2][SW], nsa[2][SW], nsb[2][SW];
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+
+#define LOAD_GLOBAL(step)                                                                      \
+  do {                                                                                         \
+    const int k_ = (step) * MX_ROW_BYTES + kc * 16;                                            \
+    _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                            \
+      const int ra_ = row0 + lr + 32 * q, rb_ = col0 + lr + 32 * q;                            \
+      ga[q] = (ra_ < M && k_ < KB) ? *reinterpret_cast<const u32x4*>(A + static_cast<size_t>(ra_) * KB + k_) : zero; \
+      gb[q] = (rb_ < N && k_ < KB) ? *reinterpret_cast<const u32x4*>(B + static_cast<size_t>(rb_) * KB + k_) : zero; \
+    }                                                                                          \
+    _Pragma("unroll") for (int bl = 0; bl < 2; ++bl)                                           \
+      _Pragma("unroll") for (int p = 0; p < SW; ++p) {                                         \
+        const int kb_ = ((step) * SW + p) * 4;                                                 \
+        nsa[bl][p] = load_scale_word(SA, row0 + wm * 64 + bl * 32 + l32, M, KS, kb_) >> (8 * half); \
+        nsb[bl][p] = load_scale_word(SB, col0 + wn * 64 + bl * 32 + l32, N, KS, kb_) >> (8 * half); \
+      }                                                                                        \
+  } while (0)
+#define STORE_LDS(stage)                                                                       \
+  do {                                                                                         \
+    unsigned char* d_ = lds + (stage) * 2 * MX_STAGE_BYTES + lr * MX_ROW_BYTES + wch * 16;     \
+    _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                            \
+      *reinterpret_cast<u32x4*>(d_ + 32 * q * MX_ROW_BYTES) = ga[q];                           \
+      *reinterpret_cast<u32x4*>(d_ + MX_STAGE_BYTES + 32 * q * MX_ROW_BYTES) = gb[q];          \
+    }                                                                                          \
+    _Pragma("unroll") for (int bl = 0; bl < 2; ++bl)                                           \
+      _Pragma("unroll") for (int p = 0; p < SW; ++p) {                                         \
+        sa[bl][p] = nsa[bl][p];                                                                \
+        sb[bl][p] = nsb[bl][p];                                                                \
+      }                                                                                        \
+  } while (0)
+
+  f32x16 acc[2][2];
 #pragma unroll
   for (int bm = 0; bm < 2; ++bm)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float rs = acc[bm][0][r] + acc[bm][1][r];
+    for (int bn = 0; bn < 2; ++bn)
 #pragma unroll
-      for (int off = 16; off >= 1; off >>= 1) rs += __shfl_xor(rs, off);
-      if (l32 == 0) red[2 * TILE + wn * TILE + wm * 64 + bm * 32 + 8 * (r >> 2) + 4 * half + (r & 3)] = rs;
-    }
-  __syncthreads();
-  if (t < TILE) {
-    if (col0 + t < N) colsum[static_cast<size_t>(tm) * N + col0 + t] = red[t] + red[TILE + t];
-  } else {
-    const int u = t - TILE;
-    if (row0 + u < M) rowsum[static_cast<size_t>(tn) * M + row0 + u] = red[2 * TILE + u] + red[3 * TILE + u];
-  }
+      for (int r = 0; r < 16; ++r) acc[bm][bn][r] = 0.0f;
 
-  if (C != nullptr) {  // --c-out only; the production run never stores M x N
+  // the lane's chunk of instruction kk is 2 * CPI * kk + half (+ 2 for fp8's second read),
+  // xored with the key of its row: fold half and key into one per-lane term
+  const int xs = (l32 & 7) ^ ((l32 >> 3) & 1) ^ half;
+  const int nsteps = (KB + MX_ROW_BYTES - 1) / MX_ROW_BYTES;
+  LOAD_GLOBAL(0);
+  STORE_LDS(0);
+  __syncthreads();
+  for (int s = 0; s < nsteps; ++s) {
+    const int stage = s & 1;
+    const bool more = s + 1 < nsteps;
+    const unsigned char* pa = lds + stage * 2 * MX_STAGE_BYTES + (wm * 64 + l32) * MX_ROW_BYTES;
+    const unsigned char* pb = lds + stage * 2 * MX_STAGE_BYTES + MX_STAGE_BYTES + (wn * 64 + l32) * MX_ROW_BYTES;
+    if (more) LOAD_GLOBAL(s + 1);  // elements and scales in flight while this step multiplies
 #pragma unroll
-    for (int bm = 0; bm < 2; ++bm)
-#pragma unroll
-      for (int bn = 0; bn < 2; ++bn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = lane_row + bm * 32 + 8 * (r >> 2) + (r & 3), col = lane_col + bn * 32;
-          if (row < M && col < N) C[static_cast<size_t>(row) * N + col] = acc[bm][bn][r];
-        }
+    for (int p = 0; p < SW; ++p) {
+      mx_mfma_2x2<FMT, 0>(pa, pb, (4 * p * CPI) ^ xs, sa[0][p], sa[1][p], sb[0][p], sb[1][p], acc);
+      mx_mfma_2x2<FMT, 2>(pa, pb, ((4 * p + 2) * CPI) ^ xs, sa[0][p], sa[1][p], sb[0][p], sb[1][p], acc);
+    }
+    // the other stage was last read in step s-1, before the barrier that ended it; the scale
+    // registers of this step are dead from here
+    if (more) STORE_LDS(stage ^ 1);
+    __syncthreads();
   }
+#undef LOAD_GLOBAL
+#undef STORE_LDS
+
+  abft_epilogue(acc, reinterpret_cast<float*>(lds), M, N, colsum, rowsum, C, poison_i, poison_j);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -278,6 +543,61 @@ __global__ __launch_bounds__(256) void expect_kernel(const int* __restrict__ e, 
   if (lane == 0) out[static_cast<size_t>(s) * rows_y + y] = sum;
 }
 
+// The microscaling siblings decode element and scale with integer operations into units of 1
+// (E4M3) or 1/2 (E2M1) per operand; a checksum of products is then in units of 1 or 1/4.
+template <int FMT>
+__device__ static inline int mx_units(uint32_t code) {
+  if (FMT == MXFP8) {  // s eeee mmm, bias 7: (8 + m) * 2^(e - 10), an integer for the bytes used here
+    const int e = (code >> 3) & 15, mag = e ? ((8 | (code & 7)) << e) >> 10 : 0;
+    return (code & 0x80u) ? -mag : mag;
+  }
+  // s ee m, bias 1, in halves: m when e == 0 (the subnormal), else (2 + m) * 2^(e - 1)
+  const int e = (code >> 1) & 3, m = code & 1, mag = e ? (2 | m) << (e - 1) : m;
+  return (code & 8u) ? -mag : mag;
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void stripe_sum_mx_kernel(const unsigned char* __restrict__ X,
+                                                            const unsigned char* __restrict__ S, int rows, int K,
+                                                            int* __restrict__ e) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
+  if (k >= K) return;
+  const int end = min(rows, (s + 1) * TILE);
+  int sum = 0;
+  for (int i = s * TILE; i < end; ++i) {
+    const size_t at = static_cast<size_t>(i) * K + k;
+    const uint32_t code = FMT == MXFP8 ? X[at] : (X[at / 2] >> (4 * (k & 1))) & 15u;
+    sum += mx_units<FMT>(code) * (1 << (S[at / 32] - 127));
+  }
+  e[static_cast<size_t>(s) * K + k] = sum;
+}
+
+// one wave per (y, s) as in expect_kernel; a lane's 8 k lie in one scale block
+template <int FMT>
+__global__ __launch_bounds__(256) void expect_mx_kernel(const int* __restrict__ e, int stripes,
+                                                        const unsigned char* __restrict__ Y,
+                                                        const unsigned char* __restrict__ SY, int rows_y, int K,
+                                                        int* __restrict__ out) {
+  constexpr int BITS = FMT == MXFP8 ? 8 : 4;
+  const int lane = threadIdx.x & 63, s = blockIdx.y * 4 + (threadIdx.x >> 6), y = blockIdx.x;
+  if (s >= stripes) return;  // whole waves leave; no barrier below
+  const unsigned char* yr = Y + static_cast<size_t>(y) * K * BITS / 8;
+  const unsigned char* sr = SY + static_cast<size_t>(y) * (K / 32);
+  const int* er = e + static_cast<size_t>(s) * K;
+  int sum = 0;
+  for (int k = lane * 8; k < K; k += 512) {
+    uint64_t v = *reinterpret_cast<const uint32_t*>(yr + k * BITS / 8);
+    if (FMT == MXFP8) v |= static_cast<uint64_t>(*reinterpret_cast<const uint32_t*>(yr + k + 4)) << 32;
+    int part = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) part += er[k + j] * mx_units<FMT>(static_cast<uint32_t>(v >> (BITS * j)) & ((1u << BITS) - 1u));
+    sum += part * (1 << (sr[k >> 5] - 127));
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
+  if (lane == 0) out[static_cast<size_t>(s) * rows_y + y] = sum;
+}
+
 constexpr int MAX_RECORDS = 16;
 
 struct Suspect {  // one checksum that disagrees
@@ -297,19 +617,20 @@ struct GemmResult {
 
 __global__ __launch_bounds__(256) void verify_kernel(const float* __restrict__ colsum, const int* __restrict__ colexp,
                                                      size_t ncol, int N, const float* __restrict__ rowsum,
-                                                     const int* __restrict__ rowexp, size_t nrow, int M, GemmResult* res) {
+                                                     const int* __restrict__ rowexp, size_t nrow, int M, float unit,
+                                                     GemmResult* res) {
   const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
   for (size_t x = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; x < ncol + nrow; x += stride) {
     const bool is_col = x < ncol;
     const size_t y = is_col ? x : x - ncol;
-    const float got = is_col ? colsum[y] : rowsum[y];
+    const float got = (is_col ? colsum[y] : rowsum[y]) * unit;  // in the units of `want`: exact, a power of two
     const float want = static_cast<float>(is_col ? colexp[y] : rowexp[y]);
     if (got == want) continue;  // a NaN is a mismatch
     atomicAdd(&res->count, 1u);
     const unsigned int slot = atomicAdd(is_col ? &res->ncol : &res->nrow, 1u);
     if (slot < MAX_RECORDS) {
       const int width = is_col ? N : M;
-      Suspect sus = {static_cast<int>(y / width), static_cast<int>(y % width), got - want};
+      Suspect sus = {static_cast<int>(y / width), static_cast<int>(y % width), (got - want) / unit};
       (is_col ? res->col : res->row)[slot] = sus;
     }
   }
@@ -417,7 +738,8 @@ static int grid_for(int dev) {
 
 static int usage(const char* why) {
   fprintf(stderr,
-          "%s\nusage: gpu_check gemm --m M --n N --k K [--seed S] [--a FILE --b FILE] [--c-out FILE] [--poison I,J] "
+          "%s\nusage: gpu_check gemm [--dtype bf16|mxfp8|mxfp4] --m M --n N --k K [--seed S] "
+          "[--a FILE --b FILE [--sa FILE --sb FILE]] [--c-out FILE] [--poison I,J] "
           "[--device D] [--seconds T]\n       gpu_check hbm --mib SIZE [--passes P] [--seed S] [--flip WORD:MASK] "
           "[--device D]\n",
           why);
@@ -438,38 +760,123 @@ static bool read_operand(const std::string& path, size_t elems, std::vector<uint
   return true;
 }
 
-static int run_gemm(int M, int N, int K, uint32_t seed, const std::string& a_file, const std::string& b_file,
-                    const std::string& c_out, int poison_i, int poison_j, int device, double seconds) {
-  if (M <= 0 || N <= 0 || K <= 0 || M % 32 || N % 32 || K % 16 || K > 32768)
+// exactly `bytes` raw bytes of a microscaling operand; `kind` is MXFP8 (E4M3 bytes of -2 .. 2),
+// MXFP4 (two E2M1 codes of magnitude 0 .. 4 per byte, no negative zero) or 0 (scales: 127, 128)
+static bool read_mx(const std::string& path, size_t bytes, int kind, std::vector<unsigned char>* out) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return false;
+  out->resize(bytes);
+  const size_t got = fread(out->data(), 1, bytes, f);
+  const bool exact = got == bytes && fgetc(f) == EOF;
+  fclose(f);
+  if (!exact) return false;
+  const auto fp4 = [](unsigned c) { return (c & 7u) <= 4u && c != 8u; };
+  for (unsigned char b : *out) {
+    const bool good = kind == MXFP8   ? (b == 0x00 || b == 0x38 || b == 0x40 || b == 0xb8 || b == 0xc0)
+                      : kind == MXFP4 ? (fp4(b & 15u) && fp4(b >> 4))
+                                      : (b == 127 || b == 128);
+    if (!good) return false;
+  }
+  return true;
+}
+
+struct GemmBuffers {
+  unsigned char *A, *B, *SA, *SB;  // the scales only for the microscaling formats
+  float *colsum, *rowsum, *C;
+  int *ea, *eb, *colexp, *rowexp;
+};
+
+// One pass: fresh inputs when asked, the GEMM between the two events, the expected checksums.
+template <int FMT>
+static void gemm_pass(const GemmBuffers& g, int M, int N, int K, int grid, bool generate, uint32_t s, int poison_i,
+                      int poison_j, hipEvent_t ev0, hipEvent_t ev1) {
+  const int tiles_m = (M + TILE - 1) / TILE, tiles_n = (N + TILE - 1) / TILE;
+  const dim3 tiles(tiles_n, tiles_m), b256(256), kx_m((K + 255) / 256, tiles_m), kx_n((K + 255) / 256, tiles_n);
+  const dim3 ex_col(N, (tiles_m + 3) / 4), ex_row(M, (tiles_n + 3) / 4);
+  if constexpr (FMT == BF16) {
+    uint16_t *A = reinterpret_cast<uint16_t*>(g.A), *B = reinterpret_cast<uint16_t*>(g.B);
+    if (generate) {
+      hipLaunchKernelGGL(generate_kernel, dim3(grid), b256, 0, 0, A, M, K, mix32(2 * s));
+      hipLaunchKernelGGL(generate_kernel, dim3(grid), b256, 0, 0, B, N, K, mix32(2 * s + 1));
+    }
+    CHECK(hipEventRecord(ev0));
+    hipLaunchKernelGGL(gemm_abft_kernel, tiles, b256, 0, 0, A, B, M, N, K, g.colsum, g.rowsum, g.C, poison_i, poison_j);
+    CHECK(hipEventRecord(ev1));
+    hipLaunchKernelGGL(stripe_sum_kernel, kx_m, b256, 0, 0, A, M, K, g.ea);
+    hipLaunchKernelGGL(stripe_sum_kernel, kx_n, b256, 0, 0, B, N, K, g.eb);
+    hipLaunchKernelGGL(expect_kernel, ex_col, b256, 0, 0, g.ea, tiles_m, B, N, K, g.colexp);
+    hipLaunchKernelGGL(expect_kernel, ex_row, b256, 0, 0, g.eb, tiles_n, A, M, K, g.rowexp);
+  } else {
+    if (generate) {
+      hipLaunchKernelGGL(generate_mx_kernel<FMT>, dim3(grid), b256, 0, 0, g.A, M, K, mix32(2 * s));
+      hipLaunchKernelGGL(generate_mx_kernel<FMT>, dim3(grid), b256, 0, 0, g.B, N, K, mix32(2 * s + 1));
+      hipLaunchKernelGGL(generate_scale_kernel, dim3(grid), b256, 0, 0, g.SA, M, K / 32, mix32(2 * s));
+      hipLaunchKernelGGL(generate_scale_kernel, dim3(grid), b256, 0, 0, g.SB, N, K / 32, mix32(2 * s + 1));
+    }
+    CHECK(hipEventRecord(ev0));
+    hipLaunchKernelGGL(gemm_abft_mx_kernel<FMT>, tiles, b256, 0, 0, g.A, g.B, g.SA, g.SB, M, N, K, g.colsum, g.rowsum,
+                       g.C, poison_i, poison_j);
+    CHECK(hipEventRecord(ev1));
+    hipLaunchKernelGGL(stripe_sum_mx_kernel<FMT>, kx_m, b256, 0, 0, g.A, g.SA, M, K, g.ea);
+    hipLaunchKernelGGL(stripe_sum_mx_kernel<FMT>, kx_n, b256, 0, 0, g.B, g.SB, N, K, g.eb);
+    hipLaunchKernelGGL(expect_mx_kernel<FMT>, ex_col, b256, 0, 0, g.ea, tiles_m, g.B, g.SB, N, K, g.colexp);
+    hipLaunchKernelGGL(expect_mx_kernel<FMT>, ex_row, b256, 0, 0, g.eb, tiles_n, g.A, g.SA, M, K, g.rowexp);
+  }
+}
+
+static int run_gemm(int fmt, int M, int N, int K, uint32_t seed, const std::string& a_file, const std::string& b_file,
+                    const std::string& sa_file, const std::string& sb_file, const std::string& c_out, int poison_i,
+                    int poison_j, int device, double seconds) {
+  if (fmt == BF16 && (M <= 0 || N <= 0 || K <= 0 || M % 32 || N % 32 || K % 16 || K > 32768))
     return usage("gemm: M and N must be multiples of 32, K a multiple of 16 and at most 32768");
+  // the caps of the exactness argument in the header: 16*K*128 and 64*K*128 quarter-units <= 2^24
+  if (fmt != BF16 && (M <= 0 || N <= 0 || K <= 0 || M % 32 || N % 32 || K % 64 || K > (fmt == MXFP8 ? 8192 : 2048)))
+    return usage("gemm: M and N must be multiples of 32, K a multiple of 64 and at most 8192 (mxfp8) or 2048 (mxfp4)");
   if (a_file.empty() != b_file.empty()) return usage("gemm: --a and --b go together");
+  if (fmt == BF16 ? !(sa_file.empty() && sb_file.empty())
+                  : (sa_file.empty() != a_file.empty() || sb_file.empty() != a_file.empty()))
+    return usage("gemm: --sa and --sb go with --a and --b, for the mx types only");
   if (poison_i >= M || poison_j >= N) return usage("gemm: --poison outside C");
   const size_t a_elems = static_cast<size_t>(M) * K, b_elems = static_cast<size_t>(N) * K;
+  const size_t a_bytes = fmt == BF16 ? a_elems * 2 : fmt == MXFP8 ? a_elems : a_elems / 2;
+  const size_t b_bytes = fmt == BF16 ? b_elems * 2 : fmt == MXFP8 ? b_elems : b_elems / 2;
   std::vector<uint16_t> ha, hb;
-  if (!a_file.empty() && !(read_operand(a_file, a_elems, &ha) && read_operand(b_file, b_elems, &hb)))
+  std::vector<unsigned char> xa, xb, hsa, hsb;
+  if (fmt == BF16 && !a_file.empty() && !(read_operand(a_file, a_elems, &ha) && read_operand(b_file, b_elems, &hb)))
     return usage("gemm: --a/--b must hold exactly M*K and N*K bf16 integers in [-2, 2]");
+  if (fmt != BF16 && !a_file.empty() &&
+      !(read_mx(a_file, a_bytes, fmt, &xa) && read_mx(b_file, b_bytes, fmt, &xb) &&
+        read_mx(sa_file, a_elems / 32, 0, &hsa) && read_mx(sb_file, b_elems / 32, 0, &hsb)))
+    return usage("gemm: --a/--b must hold exactly M*K and N*K E4M3 bytes of -2 .. 2 (mxfp8) or E2M1 codes of 0 .. 2 "
+                 "in halves (mxfp4), --sa/--sb M*K/32 and N*K/32 bytes of 127 or 128");
 
   CHECK(hipSetDevice(device));
   const int grid = grid_for(device);
   const int tiles_m = (M + TILE - 1) / TILE, tiles_n = (N + TILE - 1) / TILE;
   const size_t ncol = static_cast<size_t>(tiles_m) * N, nrow = static_cast<size_t>(tiles_n) * M;
-  uint16_t *A = nullptr, *B = nullptr;
-  float *colsum = nullptr, *rowsum = nullptr, *C = nullptr;
-  int *ea = nullptr, *eb = nullptr, *colexp = nullptr, *rowexp = nullptr;
+  GemmBuffers g = {};
   GemmResult* res = nullptr;
-  CHECK(hipMalloc(&A, a_elems * 2));
-  CHECK(hipMalloc(&B, b_elems * 2));
-  CHECK(hipMalloc(&colsum, ncol * 4));
-  CHECK(hipMalloc(&rowsum, nrow * 4));
-  CHECK(hipMalloc(&colexp, ncol * 4));
-  CHECK(hipMalloc(&rowexp, nrow * 4));
-  CHECK(hipMalloc(&ea, static_cast<size_t>(tiles_m) * K * 4));
-  CHECK(hipMalloc(&eb, static_cast<size_t>(tiles_n) * K * 4));
+  CHECK(hipMalloc(&g.A, a_bytes));
+  CHECK(hipMalloc(&g.B, b_bytes));
+  if (fmt != BF16) {
+    CHECK(hipMalloc(&g.SA, a_elems / 32));
+    CHECK(hipMalloc(&g.SB, b_elems / 32));
+  }
+  CHECK(hipMalloc(&g.colsum, ncol * 4));
+  CHECK(hipMalloc(&g.rowsum, nrow * 4));
+  CHECK(hipMalloc(&g.colexp, ncol * 4));
+  CHECK(hipMalloc(&g.rowexp, nrow * 4));
+  CHECK(hipMalloc(&g.ea, static_cast<size_t>(tiles_m) * K * 4));
+  CHECK(hipMalloc(&g.eb, static_cast<size_t>(tiles_n) * K * 4));
   CHECK(hipMalloc(&res, sizeof(GemmResult)));
-  if (!c_out.empty()) CHECK(hipMalloc(&C, static_cast<size_t>(M) * N * 4));
+  if (!c_out.empty()) CHECK(hipMalloc(&g.C, static_cast<size_t>(M) * N * 4));
   if (!a_file.empty()) {
-    CHECK(hipMemcpy(A, ha.data(), a_elems * 2, hipMemcpyHostToDevice));
-    CHECK(hipMemcpy(B, hb.data(), b_elems * 2, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(g.A, fmt == BF16 ? static_cast<const void*>(ha.data()) : xa.data(), a_bytes, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(g.B, fmt == BF16 ? static_cast<const void*>(hb.data()) : xb.data(), b_bytes, hipMemcpyHostToDevice));
+    if (fmt != BF16) {
+      CHECK(hipMemcpy(g.SA, hsa.data(), hsa.size(), hipMemcpyHostToDevice));
+      CHECK(hipMemcpy(g.SB, hsb.data(), hsb.size(), hipMemcpyHostToDevice));
+    }
   }
   hipEvent_t ev0, ev1;
   CHECK(hipEventCreate(&ev0));
@@ -478,23 +885,17 @@ static int run_gemm(int M, int N, int K, uint32_t seed, const std::string& a_fil
   GemmResult host = {};
   int passes = 0;
   double gemm_ms = 0.0;
+  float* const C = g.C;
   const auto t0 = std::chrono::steady_clock::now();
   do {
-    if (a_file.empty()) {
-      const uint32_t s = seed + static_cast<uint32_t>(passes);
-      hipLaunchKernelGGL(generate_kernel, dim3(grid), dim3(256), 0, 0, A, M, K, mix32(2 * s));
-      hipLaunchKernelGGL(generate_kernel, dim3(grid), dim3(256), 0, 0, B, N, K, mix32(2 * s + 1));
-    }
+    const uint32_t s = seed + static_cast<uint32_t>(passes);
     CHECK(hipMemset(res, 0, sizeof(GemmResult)));
-    CHECK(hipEventRecord(ev0));
-    hipLaunchKernelGGL(gemm_abft_kernel, dim3(tiles_n, tiles_m), dim3(256), 0, 0, A, B, M, N, K, colsum, rowsum, C,
-                       poison_i, poison_j);
-    CHECK(hipEventRecord(ev1));
-    hipLaunchKernelGGL(stripe_sum_kernel, dim3((K + 255) / 256, tiles_m), dim3(256), 0, 0, A, M, K, ea);
-    hipLaunchKernelGGL(stripe_sum_kernel, dim3((K + 255) / 256, tiles_n), dim3(256), 0, 0, B, N, K, eb);
-    hipLaunchKernelGGL(expect_kernel, dim3(N, (tiles_m + 3) / 4), dim3(256), 0, 0, ea, tiles_m, B, N, K, colexp);
-    hipLaunchKernelGGL(expect_kernel, dim3(M, (tiles_n + 3) / 4), dim3(256), 0, 0, eb, tiles_n, A, M, K, rowexp);
-    hipLaunchKernelGGL(verify_kernel, dim3(grid), dim3(256), 0, 0, colsum, colexp, ncol, N, rowsum, rowexp, nrow, M, res);
+    if (fmt == BF16) gemm_pass<BF16>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
+    else if (fmt == MXFP8) gemm_pass<MXFP8>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
+    else gemm_pass<MXFP4>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
+    // the mxfp4 checksums are compared in quarter-units
+    hipLaunchKernelGGL(verify_kernel, dim3(grid), dim3(256), 0, 0, g.colsum, g.colexp, ncol, N, g.rowsum, g.rowexp, nrow,
+                       M, fmt == MXFP4 ? 4.0f : 1.0f, res);
     hipLaunchKernelGGL(locate_kernel, dim3(1), dim3(1), 0, 0, res, tiles_n);
     CHECK(hipGetLastError());
     CHECK(hipMemcpy(&host, res, sizeof(GemmResult), hipMemcpyDeviceToHost));
@@ -525,9 +926,10 @@ static int run_gemm(int M, int N, int K, uint32_t seed, const std::string& a_fil
     recs += (r ? "," : "") + std::string(buf);
   }
   const double tflops = gemm_ms > 0 ? 2.0 * M * N * K * passes / (gemm_ms * 1e-3) / 1e12 : 0.0;
-  printf("{\"check\":\"gemm\",\"ok\":%s,\"m\":%d,\"n\":%d,\"k\":%d,\"passes\":%d,\"mismatch_count\":%u,\"mismatches\":[%s],"
+  printf("{\"check\":\"gemm\",%s\"ok\":%s,\"m\":%d,\"n\":%d,\"k\":%d,\"passes\":%d,\"mismatch_count\":%u,\"mismatches\":[%s],"
          "\"tflops\":%.3f}\n",
-         ok ? "true" : "false", M, N, K, passes, host.count, recs.c_str(), tflops);
+         fmt == MXFP8 ? "\"dtype\":\"mxfp8\"," : fmt == MXFP4 ? "\"dtype\":\"mxfp4\"," : "", ok ? "true" : "false", M, N, K,
+         passes, host.count, recs.c_str(), tflops);
   return ok ? 0 : 1;
 }
 
@@ -598,12 +1000,12 @@ int main(int argc, char** argv) {
   const std::string mode = argv[1];
   if (mode != "gemm" && mode != "hbm") return usage("unknown subcommand");
   g_check = mode == "gemm" ? "gemm" : "hbm";
-  int M = 8192, N = 8192, K = 4096, device = 0, passes = 2, poison_i = -1, poison_j = -1;
+  int fmt = BF16, M = 8192, N = 8192, K = 0, device = 0, passes = 2, poison_i = -1, poison_j = -1;
   double seconds = 2.0, mib = 0.0;
   uint32_t seed = 1, flip_mask = 0;
   unsigned long long flip_word = 0;
   bool flip = false;
-  std::string a_file, b_file, c_out;
+  std::string a_file, b_file, sa_file, sb_file, c_out;
   for (int i = 2; i < argc; i += 2) {
     const std::string k = argv[i];
     if (i + 1 >= argc) return usage(("option " + k + " needs a value").c_str());
@@ -617,6 +1019,13 @@ int main(int argc, char** argv) {
     else if (gemm && k == "--k") K = atoi(v);
     else if (gemm && k == "--a") a_file = v;
     else if (gemm && k == "--b") b_file = v;
+    else if (gemm && k == "--sa") sa_file = v;
+    else if (gemm && k == "--sb") sb_file = v;
+    else if (gemm && k == "--dtype") {
+      const std::string d = v;
+      if (d != "bf16" && d != "mxfp8" && d != "mxfp4") return usage("--dtype wants bf16, mxfp8 or mxfp4");
+      fmt = d == "bf16" ? BF16 : d == "mxfp8" ? MXFP8 : MXFP4;
+    }
     else if (gemm && k == "--c-out") c_out = v;
     else if (gemm && k == "--seconds") seconds = atof(v);
     else if (gemm && k == "--poison") {
@@ -637,6 +1046,8 @@ int main(int argc, char** argv) {
     } else return usage(("unknown option " + k).c_str());
   }
   if (device < 0) return usage("--device must not be negative");
-  if (mode == "gemm") return run_gemm(M, N, K, seed, a_file, b_file, c_out, poison_i, poison_j, device, seconds);
+  if (K == 0) K = fmt == BF16 ? 4096 : fmt == MXFP8 ? 8192 : 2048;  // the default: for the mx types the format's cap
+  if (mode == "gemm")
+    return run_gemm(fmt, M, N, K, seed, a_file, b_file, sa_file, sb_file, c_out, poison_i, poison_j, device, seconds);
   return run_hbm(mib, passes, seed, flip, flip_word, flip_mask, device);
 }

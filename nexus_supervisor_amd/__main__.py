@@ -81,9 +81,15 @@ def main(argv=None) -> int:
         ap.add_argument("--device", type=int, default=0)
         ap.add_argument("--quick", action="store_true", help="1024^3 GEMM, one pass, 256 MiB of HBM")
         ap.add_argument("--json", action="store_true", help="print the whole record")
+        ap.add_argument("--dtypes", default="bf16", help="GEMM formats, comma-separated: bf16[,mxfp8][,mxfp4]")
+        ap.add_argument("--all-formats", action="store_true", help="the same as --dtypes bf16,mxfp8,mxfp4")
         a = ap.parse_args(argv)
         quick = {"gemm": (1024, 1024, 1024), "seconds": 0.0, "hbm_mib": 256.0} if a.quick else {}
-        result = check_gpu(a.device, **quick)
+        dtypes = ("bf16", "mxfp8", "mxfp4") if a.all_formats else tuple(a.dtypes.split(","))
+        try:
+            result = check_gpu(a.device, dtypes=dtypes, **quick)
+        except ValueError as e:
+            ap.error(str(e))
         print(json.dumps(result) if a.json else summarize(result))
         return 0 if result["ok"] else 1
     if cmd == "version":

@@ -3,7 +3,8 @@
 Telemetry reads what amd-smi counted; this asks the device itself.  ``bin/gpu_check``
 (``csrc/health/gpu_check.hip``) runs a known-answer bf16 GEMM on the matrix units, checked
 exactly by on-device checksums, and a moving-inversions sweep over HBM.  Both answers are
-exact: pass and fail need no tolerance.
+exact: pass and fail need no tolerance.  On request the same GEMM check also runs in the
+microscaling formats (MXFP8, MXFP4) on the scaled matrix path, which the bf16 one never touches.
 
 The checks run as child processes, one after the other.  The caller (a long-lived agent)
 never opens the GPU itself, so it never shows in amd-smi's process list, and a child that
@@ -45,15 +46,25 @@ def _run_step(cmd: List[str], timeout: float) -> Tuple[Dict[str, Any], Optional[
     return rec, f"exit {p.returncode}: {rec.get('error', 'no reason given')}", False
 
 
+# the largest K at which the binary's exactness argument holds, per microscaling format
+# (``run_gemm`` in csrc/health/gpu_check.hip enforces the same)
+MX_K_CAP = {"mxfp8": 8192, "mxfp4": 2048}
+
+
 def check_gpu(device: int = 0, *, gemm: Sequence[int] = (8192, 8192, 4096), seconds: float = 2.0,
               hbm_mib: Optional[float] = None, passes: int = 2, timeout: float = 120.0,
-              binary: Optional[str] = None) -> Dict[str, Any]:
+              binary: Optional[str] = None, dtypes: Sequence[str] = ("bf16",)) -> Dict[str, Any]:
     """Run the GEMM check, then the HBM check, on ``device``.  ``hbm_mib=None`` lets the
     binary size the sweep (the smaller of 32 GiB and half of what is free); ``binary``
-    overrides the built ``bin/gpu_check``.  Returns ``{"ok", "device", "gemm", "hbm",
-    "elapsed_s", "error"}``: ``ok`` only if both children exited 0 and said ok; ``error``
-    names the step that failed and how.  The HBM step is skipped when the GEMM step ended
-    by signal or timeout."""
+    overrides the built ``bin/gpu_check``.  ``dtypes`` names the GEMM formats: ``"bf16"``
+    always, and each of ``"mxfp8"``, ``"mxfp4"`` adds one child after it with the same M and N
+    and K capped at ``MX_K_CAP``, its record under ``"gemm_mxfp8"`` / ``"gemm_mxfp4"``.  Returns
+    ``{"ok", "device", "gemm", "hbm", "elapsed_s", "error"}`` and those: ``ok`` only if every
+    child exited 0 and said ok; ``error`` names the steps that failed and how.  After a step
+    that ended by signal or timeout nothing more is started: the rest is ``{"skipped": True}``."""
+    extra = [d for d in dtypes if d != "bf16"]
+    if "bf16" not in dtypes or any(d not in MX_K_CAP for d in extra) or len(set(dtypes)) != len(dtypes):
+        raise ValueError(f"dtypes must be 'bf16' and any of {sorted(MX_K_CAP)}, each once: {tuple(dtypes)!r}")
     if binary is None:
         from .. import _build
 
@@ -62,38 +73,43 @@ def check_gpu(device: int = 0, *, gemm: Sequence[int] = (8192, 8192, 4096), seco
     steps = [
         ("gemm", [binary, "gemm", "--m", str(m), "--n", str(n), "--k", str(k), "--seconds", repr(float(seconds)),
                   "--device", str(device)]),
+        *((f"gemm_{d}", [binary, "gemm", "--dtype", d, "--m", str(m), "--n", str(n), "--k", str(min(k, MX_K_CAP[d])),
+                         "--seconds", repr(float(seconds)), "--device", str(device)]) for d in extra),
         ("hbm", [binary, "hbm", "--passes", str(passes), "--device", str(device)]
          + (["--mib", repr(float(hbm_mib))] if hbm_mib is not None else [])),
     ]
-    out: Dict[str, Any] = {"ok": True, "device": device, "gemm": {}, "hbm": {}, "elapsed_s": 0.0, "error": None}
+    out: Dict[str, Any] = {"ok": True, "device": device, "gemm": {}, **{f"gemm_{d}": {} for d in extra}, "hbm": {},
+                           "elapsed_s": 0.0, "error": None}
     errors = []
     t0 = time.monotonic()
-    for name, cmd in steps:
+    for at, (name, cmd) in enumerate(steps):
         rec, err, wedged = _run_step(cmd, timeout)
         out[name] = rec
         if err:
             out["ok"] = False
             errors.append(f"{name}: {err}")
         if wedged:
-            if name == "gemm":
-                out["hbm"] = {"skipped": True}
+            for later, _ in steps[at + 1:]:
+                out[later] = {"skipped": True}
             break
     out["elapsed_s"] = round(time.monotonic() - t0, 3)
     out["error"] = "; ".join(errors) or None
     return out
 
 
-def _gemm_text(rec: Dict[str, Any]) -> str:
+def _gemm_text(rec: Dict[str, Any], label: str = "gemm") -> str:
+    if rec.get("skipped"):
+        return f"{label} not run"
     if rec.get("ok") is True:
-        return "gemm clean"
+        return f"{label} clean"
     mm = rec.get("mismatches") or []
     if not mm:
-        return "gemm failed"
+        return f"{label} failed"
     first = mm[0]
     delta = first.get("delta", 0)
     where = {"element": "C[{i},{j}]", "row": "row {i} (column stripe {stripe})",
              "column": "column {j} (row stripe {stripe})"}.get(first.get("kind"), "?")
-    text = f"gemm mismatch at {where.format(**first)} ({delta:+g}) in tile {first.get('tile')}"
+    text = f"{label} mismatch at {where.format(**first)} ({delta:+g}) in tile {first.get('tile')}"
     return text + (f" and {len(mm) - 1} more" if len(mm) > 1 else "")
 
 
@@ -112,7 +128,9 @@ def _hbm_text(rec: Dict[str, Any]) -> str:
 def summarize(result: Dict[str, Any]) -> str:
     """The one-line cause text an operator sees, e.g.
     ``gpu 0: gemm mismatch at C[37,101] (+1) in tile 0; hbm clean``."""
-    text = f"gpu {result.get('device')}: {_gemm_text(result.get('gemm') or {})}; {_hbm_text(result.get('hbm') or {})}"
+    parts = [_gemm_text(result.get("gemm") or {})]
+    parts += [_gemm_text(result[f"gemm_{d}"] or {}, f"gemm {d}") for d in MX_K_CAP if f"gemm_{d}" in result]
+    text = f"gpu {result.get('device')}: {'; '.join(parts)}; {_hbm_text(result.get('hbm') or {})}"
     # "wrong data" is already told by the mismatch; a crash, a timeout or bad output is not
     other = [e for e in (result.get("error") or "").split("; ") if e and not e.endswith(": wrong data")]
     return text + (f" [{'; '.join(other)}]" if other else "")
