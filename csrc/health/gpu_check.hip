@@ -1,6 +1,6 @@
 // gpu_check — an active device check with exact answers: "is this GPU bad, or was it the job?"
 //
-//   gpu_check gemm [--dtype bf16|mxfp8|mxfp4] --m M --n N --k K [--seed S]
+//   gpu_check gemm [--dtype bf16|mxfp8|mxfp4|fp64] --m M --n N --k K [--seed S]
 //                  [--a FILE --b FILE [--sa FILE --sb FILE]] [--c-out FILE]
 //                  [--poison I,J] [--device D] [--seconds T]
 //        bf16 x bf16 -> fp32 GEMM on the matrix units (v_mfma_f32_32x32x16_bf16), checked on
@@ -23,6 +23,17 @@
 //        Within those caps fp32 is again exact in any order and the comparison stays ==; the
 //        expected checksums are integers in units of 1 (mxfp8) or 1/4 (mxfp4).  --a/--b are
 //        raw element bytes (M*K, N*K; for mxfp4 half that), --sa/--sb the scale bytes.
+//        --dtype fp64: the same check on the double-precision matrix path
+//        (v_mfma_f64_16x16x4_f64), which none of the above touches, and on wide data.  A and B
+//        are little-endian IEEE doubles, every element an integer of magnitude <= 65535, roughly
+//        uniform over that range when generated: not five-valued.  A product is below 2^32 and a
+//        checksum over 128 rows of K products below 2^32 * K * 128 <= 2^52 for K <= 8192, so
+//        every partial sum in any order is an integer below 2^53, FP64 holds it exactly and the
+//        comparison stays ==.  M and N are multiples of 16, K a multiple of 4 and at most 8192.
+//        --a/--b hold M*K and N*K doubles (a negative zero is accepted), --c-out M*N doubles.
+//        The expected checksums come from kernels that decode the doubles' bit patterns with
+//        integer operations and add in int64: no instruction of the double-precision unit, a
+//        conversion included, is on that side.
 //   gpu_check hbm --mib SIZE [--passes P] [--seed S] [--flip WORD:MASK] [--device D]
 //        moving inversions over one allocation: pass 0 writes an address hash, each later pass
 //        loads, compares with what the pass before wrote and stores the next pattern (odd
@@ -95,7 +106,7 @@ __global__ __launch_bounds__(256) void generate_kernel(uint16_t* __restrict__ x,
 
 // The microscaling inputs, from the same hash.  X is rows x K elements; one thread writes 16
 // bytes: 16 E4M3 bytes, or 32 E2M1 nibbles (one whole scale block).  K is a multiple of 64.
-enum Fmt { BF16 = 0, MXFP8 = 1, MXFP4 = 2 };
+enum Fmt { BF16 = 0, MXFP8 = 1, MXFP4 = 2, FP64 = 3 };
 
 template <int FMT>
 __device__ static inline uint32_t small_mx_code(uint32_t seed, uint32_t row, uint32_t col) {
@@ -130,6 +141,31 @@ __global__ __launch_bounds__(256) void generate_scale_kernel(unsigned char* __re
   for (size_t x = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; x < n; x += stride) {
     const uint32_t row = static_cast<uint32_t>(x / KS), blk = static_cast<uint32_t>(x % KS);
     s[x] = 127u + (mix32(mix32(~seed ^ (row * 0x9e3779b9u)) + blk) >> 31);
+  }
+}
+
+// The FP64 inputs, from the same hash: integers roughly uniform over [-65535, 65535] as IEEE
+// double bit patterns, put together with integer operations (the data is then the same whatever
+// the double-precision unit does).  One thread writes 2 doubles (16 bytes); K is a multiple of 4.
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+
+__device__ static inline uint64_t wide_int_f64(uint32_t seed, uint32_t row, uint32_t col) {
+  const uint32_t h = mix32(mix32(seed ^ (row * 0x9e3779b9u)) + col);
+  const int v = static_cast<int>(h % 131071u) - 65535;
+  if (v == 0) return 0ull;
+  const uint32_t mag = static_cast<uint32_t>(v < 0 ? -v : v);
+  const int p = 31 - __clz(static_cast<int>(mag));  // mag = 2^p + rest
+  return (static_cast<uint64_t>(v < 0) << 63) | (static_cast<uint64_t>(1023 + p) << 52) |
+         (static_cast<uint64_t>(mag ^ (1u << p)) << (52 - p));
+}
+
+__global__ __launch_bounds__(256) void generate_f64_kernel(uint64_t* __restrict__ x, int rows, int K, uint32_t seed) {
+  const size_t chunks = static_cast<size_t>(rows) * (K / 2);
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t c = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; c < chunks; c += stride) {
+    const uint32_t row = static_cast<uint32_t>(c / (K / 2)), col = static_cast<uint32_t>(c % (K / 2)) * 2;
+    const u64x2 v = {wide_int_f64(seed, row, col), wide_int_f64(seed, row, col + 1)};
+    *reinterpret_cast<u64x2*>(x + c * 2) = v;
   }
 }
 
@@ -505,6 +541,223 @@ __global__ __launch_bounds__(256) void gemm_abft_mx_kernel(const unsigned char* 
 }
 
 // ------------------------------------------------------------------------------------------
+// The FP64 GEMM on the double-precision matrix path, with a checksum epilogue in double
+// ------------------------------------------------------------------------------------------
+
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr int F64_KSTEP = 16;                   // K advance per LDS stage
+constexpr int F64_ROW_BYTES = F64_KSTEP * 8;    // 128 B, no padding
+constexpr int F64_STAGE_BYTES = TILE * F64_ROW_BYTES;
+
+// The checksum epilogue of the FP64 kernel, from registers: a wave holds its 64x64 quadrant as
+// 4x4 blocks of 16x16 accumulators, double r of lane l holding D[4 * r + l / 16][l % 16].
+// `red` is 512 doubles of LDS that no wave reads any more.  Element (bm, bn, r) of this lane is
+//   row  row0 + wm*64 + bm*16 + 4*r + l/16,   column  col0 + wn*64 + bn*16 + l%16.
+// Every sum formed here is an integer below 2^52 (see the header), so the order does not matter.
+__device__ __forceinline__ void abft_epilogue_f64(f64x4 (&acc)[4][4], double* red, int M, int N,
+                                                  double* __restrict__ colsum, double* __restrict__ rowsum,
+                                                  double* __restrict__ C, int poison_i, int poison_j) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w >> 1, wn = w & 1;
+  const int l16 = lane & 15, grp = lane >> 4;
+  const int tn = blockIdx.x, tm = blockIdx.y;
+  const int row0 = tm * TILE, col0 = tn * TILE;
+  const int lane_row = row0 + wm * 64 + grp, lane_col = col0 + wn * 64 + l16;
+  if (poison_i >= 0) {  // detector self-test: one element off by one
+#pragma unroll
+    for (int bm = 0; bm < 4; ++bm)
+#pragma unroll
+      for (int bn = 0; bn < 4; ++bn)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool hit = lane_row + bm * 16 + 4 * r == poison_i && lane_col + bn * 16 == poison_j;
+          acc[bm][bn][r] += hit ? 1.0 : 0.0;
+        }
+  }
+
+  // red [0,256): column partials by wm; [256,512): row partials by wn
+  // column sums: over this lane's 16 doubles of a block column, then across the four lane groups
+#pragma unroll
+  for (int bn = 0; bn < 4; ++bn) {
+    double cs = 0.0;
+#pragma unroll
+    for (int bm = 0; bm < 4; ++bm)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) cs += acc[bm][bn][r];
+    cs += __shfl_xor(cs, 16);
+    cs += __shfl_xor(cs, 32);
+    if (grp == 0) red[wm * TILE + wn * 64 + bn * 16 + l16] = cs;
+  }
+  // row sums: per double over the four block columns, then a butterfly over the 16 lanes of a group
+#pragma unroll
+  for (int bm = 0; bm < 4; ++bm)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      double rs = (acc[bm][0][r] + acc[bm][1][r]) + (acc[bm][2][r] + acc[bm][3][r]);
+#pragma unroll
+      for (int off = 8; off >= 1; off >>= 1) rs += __shfl_xor(rs, off);
+      if (l16 == 0) red[2 * TILE + wn * TILE + wm * 64 + bm * 16 + 4 * r + grp] = rs;
+    }
+  __syncthreads();
+  if (t < TILE) {
+    if (col0 + t < N) colsum[static_cast<size_t>(tm) * N + col0 + t] = red[t] + red[TILE + t];
+  } else {
+    const int u = t - TILE;
+    if (row0 + u < M) rowsum[static_cast<size_t>(tn) * M + row0 + u] = red[2 * TILE + u] + red[3 * TILE + u];
+  }
+
+  if (C != nullptr) {  // --c-out only; the production run never stores M x N
+#pragma unroll
+    for (int bm = 0; bm < 4; ++bm)
+#pragma unroll
+      for (int bn = 0; bn < 4; ++bn)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = lane_row + bm * 16 + 4 * r, col = lane_col + bn * 16;
+          if (row < M && col < N) C[static_cast<size_t>(row) * N + col] = acc[bm][bn][r];
+        }
+  }
+}
+
+// Compiled for gfx950 (-O3, kernel-resource-usage): 222 VGPRs + 0 AGPRs (the 128 accumulator
+// registers are VGPRs), 65536 B LDS, 0 scratch, 0 SGPR/VGPR spills; occupancy 2 waves per SIMD,
+// asked for by the launch bounds (left alone the compiler takes 216 + 128 at occupancy 1): two
+// workgroups per CU, bounded by LDS (2 x 64 KB of 160 KB) and by registers (224 of 256) alike.
+//
+// The work split is that of the other two: one workgroup (4 waves) per 128x128 tile of C, wave
+// w the 64x64 quadrant (w / 2, w % 2), so the 128-row checksum stripes are the same.  A
+// quadrant is 4x4 blocks of v_mfma_f64_16x16x4_f64: 16 accumulators of 4 doubles, 128
+// registers per lane.
+//
+// Operand layout of the instruction (CDNA4 ISA guide, matrix arithmetic; settled on the device
+// by the one-instruction shape of the tests, with random data): lane l supplies one double,
+// A[l % 16][k = l / 16] and B[k = l / 16][l % 16]; accumulator double r of lane l holds
+// D[4 * r + l / 16][l % 16].  (Not D[4 * (l / 16) + r][l % 16], the layout of the fp32 16x16
+// instructions: a lane group's four doubles are four rows apart, not adjacent.  Products and
+// column sums are the same either way; only rows move, so data equal along a column hides it.)
+//
+// Two k per read.  A sum over k may take the k in any order, here exactly.  A lane reads the
+// 16 bytes of k = 2 * (l / 16) and 2 * (l / 16) + 1 of an 8-deep group with one ds_read_b128;
+// one instruction then takes every lane's lower double (k = 0, 2, 4, 6 of the group, the same
+// for A and B) and the next every upper one (k = 1, 3, 5, 7).  Per 8 k a wave issues 4 + 4
+// reads for 32 instructions, and every operand register pair is used four times: the a of a
+// block row against the four b, in the order (bm, bn) row by row, so that an accumulator is
+// written again only after the 15 other instructions of the sweep.
+//
+// LDS: per stage 128 rows x 16 k (128 bytes) of A and of B, two stages, 64 KB; the next
+// stage's global loads are in flight during the 64 instructions of this one.  Rows are not
+// padded; the 16-byte chunk c (two k) of row r is stored at chunk c ^ key(r),
+//   key(r) = (r >> 1) & 7,
+// an xor swizzle, but not the key of the microscaling kernel.  With 64 banks of 4 bytes a
+// 16-byte access at row r, stored chunk p, starts in the 4-bank group 8 * (r & 1) + p of 16.
+// A ds_read_b128 is served 16 lanes at a time, and these are not 16 consecutive lanes but
+// {0-3, 12-15, 20-23, 24-27}, {4-7, 8-11, 16-19, 28-31} and the same plus 32 (published for
+// CDNA3; the counter below says the same of this device).  Such a set is half of the lane
+// group l / 16 = g and half of g + 1, g even, and between them each l % 16 once: it reads
+// rows r .. r+15 (r a multiple of 16), rows 0-3 and 12-15 at chunk c = 4 * kk + g and rows
+// 4-11 at c ^ 1, or the other way round.  So row r reads stored chunk c ^ key(r) ^ m(r),
+// m = 0 or 1 and equal for the four rows of an r >> 2.  Among the 8 rows of one parity
+// key(r) is each of 0..7 once; m flips its low bit for both rows (4i, 4i + 2, or the odd
+// ones) that hold keys 2i and 2i + 1 or for neither, so these 8 rows still read 8 distinct
+// chunks, and the two parities start 8 groups apart: sixteen distinct 4-bank groups, every
+// bank once, conflict-free.  Sixteen consecutive lanes are the case m = 0.  (The key of the
+// microscaling kernel, (r & 7) ^ ((r >> 3) & 1), fails here: rows 0 and 8 then meet at m = 0
+// and 1.  Measured with it: 64 conflict cycles per wave and stage.)  The stage writes cost
+// nothing extra: 8 consecutive lanes cover the 8 chunks of a row, one 128-byte half of the
+// banks, and the next 8 lanes the row after it, the other half; served in the sets above it
+// is a half row of each of rows r .. r+3 (chunks 0-3, 4-7, 4-7, 0-3 before the xor), and the
+// keys of rows r and r + 2 differ in bit 0 only, which leaves a half row in its half.
+// SQ_LDS_BANK_CONFLICT over the whole kernel (2048 x 2048 x 1024, counters only): 0 cycles.
+// The swizzle is one xor per stage in the read address (key and l / 16 fold into one per-lane
+// term), next to 64 matrix instructions.
+//
+// Rows past M, columns past N and k past K are zero-filled in LDS, never read from memory.
+// K is a multiple of 4 and a row starts 32-byte aligned, so a 16-byte chunk of two doubles is
+// wholly inside a row or wholly outside it.
+__global__ __launch_bounds__(256, 2) void gemm_abft_f64_kernel(const double* __restrict__ A, const double* __restrict__ B,
+                                                            int M, int N, int K, double* __restrict__ colsum,
+                                                            double* __restrict__ rowsum, double* __restrict__ C,
+                                                            int poison_i, int poison_j) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * F64_STAGE_BYTES];  // [stage][A, B]
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w >> 1, wn = w & 1;
+  const int l16 = lane & 15, grp = lane >> 4;
+  const int row0 = blockIdx.y * TILE, col0 = blockIdx.x * TILE;
+
+  // global -> LDS copy as in the other kernels: a stage tile is 1024 16-byte chunks, 4 per
+  // thread per operand, rows lr + 32 q (all with the key of lr), 8 consecutive lanes per row
+  const int lr = t >> 3, kc = t & 7;
+  const int wch = kc ^ ((lr >> 1) & 7);
+  u32x4 ga[4], gb[4];
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+
+#define LOAD_GLOBAL(k0)                                                                        \
+  do {                                                                                         \
+    const int k_ = (k0) + kc * 2;                                                              \
+    _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                            \
+      const int ra_ = row0 + lr + 32 * q, rb_ = col0 + lr + 32 * q;                            \
+      ga[q] = (ra_ < M && k_ < K) ? *reinterpret_cast<const u32x4*>(A + static_cast<size_t>(ra_) * K + k_) : zero; \
+      gb[q] = (rb_ < N && k_ < K) ? *reinterpret_cast<const u32x4*>(B + static_cast<size_t>(rb_) * K + k_) : zero; \
+    }                                                                                          \
+  } while (0)
+#define STORE_LDS(stage)                                                                       \
+  do {                                                                                         \
+    unsigned char* d_ = lds + (stage) * 2 * F64_STAGE_BYTES + lr * F64_ROW_BYTES + wch * 16;   \
+    _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                            \
+      *reinterpret_cast<u32x4*>(d_ + 32 * q * F64_ROW_BYTES) = ga[q];                          \
+      *reinterpret_cast<u32x4*>(d_ + F64_STAGE_BYTES + 32 * q * F64_ROW_BYTES) = gb[q];        \
+    }                                                                                          \
+  } while (0)
+
+  f64x4 acc[4][4];
+#pragma unroll
+  for (int bm = 0; bm < 4; ++bm)
+#pragma unroll
+    for (int bn = 0; bn < 4; ++bn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[bm][bn][r] = 0.0;
+
+  // the lane's chunk of group kk is 4 * kk + grp, xored with the key of its row (that of l16,
+  // the block rows being multiples of 16): 4 * kk and grp share no bit, so it is (4 * kk) ^ xs
+  const int xs = (l16 >> 1) ^ grp;
+  const int nsteps = (K + F64_KSTEP - 1) / F64_KSTEP;
+  LOAD_GLOBAL(0);
+  STORE_LDS(0);
+  __syncthreads();
+  for (int s = 0; s < nsteps; ++s) {
+    const int stage = s & 1;
+    const bool more = s + 1 < nsteps;
+    if (more) LOAD_GLOBAL((s + 1) * F64_KSTEP);  // in flight while this step multiplies
+    const unsigned char* pa = lds + stage * 2 * F64_STAGE_BYTES + (wm * 64 + l16) * F64_ROW_BYTES;
+    const unsigned char* pb = lds + stage * 2 * F64_STAGE_BYTES + F64_STAGE_BYTES + (wn * 64 + l16) * F64_ROW_BYTES;
+#pragma unroll
+    for (int kk = 0; kk < F64_KSTEP / 8; ++kk) {
+      const int off = ((4 * kk) ^ xs) * 16;
+      f64x2 a[4], b[4];
+#pragma unroll
+      for (int bl = 0; bl < 4; ++bl) {
+        a[bl] = *reinterpret_cast<const f64x2*>(pa + bl * 16 * F64_ROW_BYTES + off);
+        b[bl] = *reinterpret_cast<const f64x2*>(pb + bl * 16 * F64_ROW_BYTES + off);
+      }
+#pragma unroll
+      for (int h = 0; h < 2; ++h)  // the even k of the group, then the odd
+#pragma unroll
+        for (int bm = 0; bm < 4; ++bm)
+#pragma unroll
+          for (int bn = 0; bn < 4; ++bn)
+            acc[bm][bn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[bm][h], b[bn][h], acc[bm][bn], 0, 0, 0);
+    }
+    // the other stage was last read in step s-1, before the barrier that ended it
+    if (more) STORE_LDS(stage ^ 1);
+    __syncthreads();
+  }
+#undef LOAD_GLOBAL
+#undef STORE_LDS
+
+  abft_epilogue_f64(acc, reinterpret_cast<double*>(lds), M, N, colsum, rowsum, C, poison_i, poison_j);
+}
+
+// ------------------------------------------------------------------------------------------
 // Expected checksums, in integer arithmetic
 // ------------------------------------------------------------------------------------------
 
@@ -598,16 +851,70 @@ __global__ __launch_bounds__(256) void expect_mx_kernel(const int* __restrict__ 
   if (lane == 0) out[static_cast<size_t>(s) * rows_y + y] = sum;
 }
 
+// The FP64 siblings share nothing with the double-precision unit: a double is decoded to its
+// integer from the bit pattern (sign, exponent, shifted significand) with integer operations,
+// never a conversion, so that no fault of that unit can cancel on both sides of the ==.
+// False when the double holds no integer of magnitude below 2^53: a fraction, an infinity, a NaN.
+__host__ __device__ static inline bool f64_int(uint64_t bits, long long* out) {
+  const int e = static_cast<int>(bits >> 52) & 0x7ff;
+  const uint64_t frac = bits & ((1ull << 52) - 1);
+  *out = 0;
+  if (e == 0) return frac == 0;             // +-0; a subnormal is a fraction
+  if (e < 1023 || e > 1075) return false;   // below 1; 2^53 and above, infinity, NaN
+  const uint64_t sig = (1ull << 52) | frac;  // the value is sig * 2^(e - 1075)
+  const int drop = 1075 - e;                 // 0 .. 52
+  if (sig & ((1ull << drop) - 1)) return false;
+  const long long mag = static_cast<long long>(sig >> drop);
+  *out = (bits >> 63) ? -mag : mag;
+  return true;
+}
+
+__device__ static inline int f64_elem(uint64_t bits) {  // an input element: validated or generated, |x| <= 65535
+  long long v;
+  f64_int(bits, &v);
+  return static_cast<int>(v);
+}
+
+// as stripe_sum_kernel; a stripe sum is at most 65535 * 128 < 2^23
+__global__ __launch_bounds__(256) void stripe_sum_f64_kernel(const uint64_t* __restrict__ X, int rows, int K,
+                                                             int* __restrict__ e) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
+  if (k >= K) return;
+  const int end = min(rows, (s + 1) * TILE);
+  int sum = 0;
+  for (int i = s * TILE; i < end; ++i) sum += f64_elem(X[static_cast<size_t>(i) * K + k]);
+  e[static_cast<size_t>(s) * K + k] = sum;
+}
+
+// one wave per (y, s) as in expect_kernel, 2 k per lane per trip (K is even); the sum is below
+// 2^23 * 2^16 * K <= 2^52 and is kept in int64
+__global__ __launch_bounds__(256) void expect_f64_kernel(const int* __restrict__ e, int stripes,
+                                                         const uint64_t* __restrict__ Y, int rows_y, int K,
+                                                         long long* __restrict__ out) {
+  const int lane = threadIdx.x & 63, s = blockIdx.y * 4 + (threadIdx.x >> 6), y = blockIdx.x;
+  if (s >= stripes) return;  // whole waves leave; no barrier below
+  const uint64_t* yr = Y + static_cast<size_t>(y) * K;
+  const int* er = e + static_cast<size_t>(s) * K;
+  long long sum = 0;
+  for (int k = lane * 2; k < K; k += 128) {
+    const u64x2 v = *reinterpret_cast<const u64x2*>(yr + k);
+    sum += static_cast<long long>(er[k]) * f64_elem(v[0]) + static_cast<long long>(er[k + 1]) * f64_elem(v[1]);
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
+  if (lane == 0) out[static_cast<size_t>(s) * rows_y + y] = sum;
+}
+
 constexpr int MAX_RECORDS = 16;
 
 struct Suspect {  // one checksum that disagrees
   int stripe, index;
-  float delta;
+  double delta;
 };
 struct GemmRecord {
   int kind;  // 0 element, 1 row, 2 column
   int i, j, tile;
-  float delta;
+  double delta;
 };
 struct GemmResult {
   unsigned int count, ncol, nrow, nrec;
@@ -631,6 +938,32 @@ __global__ __launch_bounds__(256) void verify_kernel(const float* __restrict__ c
     if (slot < MAX_RECORDS) {
       const int width = is_col ? N : M;
       Suspect sus = {static_cast<int>(y / width), static_cast<int>(y % width), (got - want) / unit};
+      (is_col ? res->col : res->row)[slot] = sus;
+    }
+  }
+}
+
+// The FP64 sibling: double sums against int64 expectations.  The sum is decoded like the inputs
+// and the == is on integers, so a sum that is no integer (a fraction, a NaN) is a mismatch too;
+// only the delta of the report is formed in double.
+__global__ __launch_bounds__(256) void verify_f64_kernel(const double* __restrict__ colsum,
+                                                         const long long* __restrict__ colexp, size_t ncol, int N,
+                                                         const double* __restrict__ rowsum,
+                                                         const long long* __restrict__ rowexp, size_t nrow, int M,
+                                                         GemmResult* res) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t x = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; x < ncol + nrow; x += stride) {
+    const bool is_col = x < ncol;
+    const size_t y = is_col ? x : x - ncol;
+    const double got = is_col ? colsum[y] : rowsum[y];
+    const long long want = is_col ? colexp[y] : rowexp[y];
+    long long have;
+    if (f64_int(static_cast<uint64_t>(__double_as_longlong(got)), &have) && have == want) continue;
+    atomicAdd(&res->count, 1u);
+    const unsigned int slot = atomicAdd(is_col ? &res->ncol : &res->nrow, 1u);
+    if (slot < MAX_RECORDS) {
+      const int width = is_col ? N : M;
+      Suspect sus = {static_cast<int>(y / width), static_cast<int>(y % width), got - static_cast<double>(want)};
       (is_col ? res->col : res->row)[slot] = sus;
     }
   }
@@ -738,9 +1071,10 @@ static int grid_for(int dev) {
 
 static int usage(const char* why) {
   fprintf(stderr,
-          "%s\nusage: gpu_check gemm [--dtype bf16|mxfp8|mxfp4] --m M --n N --k K [--seed S] "
+          "%s\nusage: gpu_check gemm [--dtype bf16|mxfp8|mxfp4|fp64] --m M --n N --k K [--seed S] "
           "[--a FILE --b FILE [--sa FILE --sb FILE]] [--c-out FILE] [--poison I,J] "
-          "[--device D] [--seconds T]\n       gpu_check hbm --mib SIZE [--passes P] [--seed S] [--flip WORD:MASK] "
+          "[--device D] [--seconds T]\n         fp64: M and N multiples of 16, K a multiple of 4 and at most 8192; --a/--b "
+          "hold doubles, integers of magnitude <= 65535\n       gpu_check hbm --mib SIZE [--passes P] [--seed S] [--flip WORD:MASK] "
           "[--device D]\n",
           why);
   return 2;
@@ -780,10 +1114,26 @@ static bool read_mx(const std::string& path, size_t bytes, int kind, std::vector
   return true;
 }
 
+// exactly `elems` little-endian doubles, each an integer of magnitude <= 65535 (-0 is one)
+static bool read_f64(const std::string& path, size_t elems, std::vector<uint64_t>* out) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return false;
+  out->resize(elems);
+  const size_t got = fread(out->data(), 8, elems, f);
+  const bool exact = got == elems && fgetc(f) == EOF;
+  fclose(f);
+  if (!exact) return false;
+  for (uint64_t b : *out) {
+    long long v;
+    if (!f64_int(b, &v) || v < -65535 || v > 65535) return false;
+  }
+  return true;
+}
+
 struct GemmBuffers {
   unsigned char *A, *B, *SA, *SB;  // the scales only for the microscaling formats
-  float *colsum, *rowsum, *C;
-  int *ea, *eb, *colexp, *rowexp;
+  float *colsum, *rowsum, *C;      // doubles for FP64
+  int *ea, *eb, *colexp, *rowexp;  // colexp, rowexp: int64 for FP64
 };
 
 // One pass: fresh inputs when asked, the GEMM between the two events, the expected checksums.
@@ -806,6 +1156,22 @@ static void gemm_pass(const GemmBuffers& g, int M, int N, int K, int grid, bool 
     hipLaunchKernelGGL(stripe_sum_kernel, kx_n, b256, 0, 0, B, N, K, g.eb);
     hipLaunchKernelGGL(expect_kernel, ex_col, b256, 0, 0, g.ea, tiles_m, B, N, K, g.colexp);
     hipLaunchKernelGGL(expect_kernel, ex_row, b256, 0, 0, g.eb, tiles_n, A, M, K, g.rowexp);
+  } else if constexpr (FMT == FP64) {
+    uint64_t *A = reinterpret_cast<uint64_t*>(g.A), *B = reinterpret_cast<uint64_t*>(g.B);
+    long long *colexp = reinterpret_cast<long long*>(g.colexp), *rowexp = reinterpret_cast<long long*>(g.rowexp);
+    if (generate) {
+      hipLaunchKernelGGL(generate_f64_kernel, dim3(grid), b256, 0, 0, A, M, K, mix32(2 * s));
+      hipLaunchKernelGGL(generate_f64_kernel, dim3(grid), b256, 0, 0, B, N, K, mix32(2 * s + 1));
+    }
+    CHECK(hipEventRecord(ev0));
+    hipLaunchKernelGGL(gemm_abft_f64_kernel, tiles, b256, 0, 0, reinterpret_cast<const double*>(A),
+                       reinterpret_cast<const double*>(B), M, N, K, reinterpret_cast<double*>(g.colsum),
+                       reinterpret_cast<double*>(g.rowsum), reinterpret_cast<double*>(g.C), poison_i, poison_j);
+    CHECK(hipEventRecord(ev1));
+    hipLaunchKernelGGL(stripe_sum_f64_kernel, kx_m, b256, 0, 0, A, M, K, g.ea);
+    hipLaunchKernelGGL(stripe_sum_f64_kernel, kx_n, b256, 0, 0, B, N, K, g.eb);
+    hipLaunchKernelGGL(expect_f64_kernel, ex_col, b256, 0, 0, g.ea, tiles_m, B, N, K, colexp);
+    hipLaunchKernelGGL(expect_f64_kernel, ex_row, b256, 0, 0, g.eb, tiles_n, A, M, K, rowexp);
   } else {
     if (generate) {
       hipLaunchKernelGGL(generate_mx_kernel<FMT>, dim3(grid), b256, 0, 0, g.A, M, K, mix32(2 * s));
@@ -830,21 +1196,29 @@ static int run_gemm(int fmt, int M, int N, int K, uint32_t seed, const std::stri
   if (fmt == BF16 && (M <= 0 || N <= 0 || K <= 0 || M % 32 || N % 32 || K % 16 || K > 32768))
     return usage("gemm: M and N must be multiples of 32, K a multiple of 16 and at most 32768");
   // the caps of the exactness argument in the header: 16*K*128 and 64*K*128 quarter-units <= 2^24
-  if (fmt != BF16 && (M <= 0 || N <= 0 || K <= 0 || M % 32 || N % 32 || K % 64 || K > (fmt == MXFP8 ? 8192 : 2048)))
+  const bool mx = fmt == MXFP8 || fmt == MXFP4;
+  if (mx && (M <= 0 || N <= 0 || K <= 0 || M % 32 || N % 32 || K % 64 || K > (fmt == MXFP8 ? 8192 : 2048)))
     return usage("gemm: M and N must be multiples of 32, K a multiple of 64 and at most 8192 (mxfp8) or 2048 (mxfp4)");
+  // 2^32 * K * 128 <= 2^52
+  if (fmt == FP64 && (M <= 0 || N <= 0 || K <= 0 || M % 16 || N % 16 || K % 4 || K > 8192))
+    return usage("gemm: M and N must be multiples of 16, K a multiple of 4 and at most 8192 (fp64)");
   if (a_file.empty() != b_file.empty()) return usage("gemm: --a and --b go together");
-  if (fmt == BF16 ? !(sa_file.empty() && sb_file.empty())
-                  : (sa_file.empty() != a_file.empty() || sb_file.empty() != a_file.empty()))
+  if (!mx ? !(sa_file.empty() && sb_file.empty())
+          : (sa_file.empty() != a_file.empty() || sb_file.empty() != a_file.empty()))
     return usage("gemm: --sa and --sb go with --a and --b, for the mx types only");
   if (poison_i >= M || poison_j >= N) return usage("gemm: --poison outside C");
   const size_t a_elems = static_cast<size_t>(M) * K, b_elems = static_cast<size_t>(N) * K;
-  const size_t a_bytes = fmt == BF16 ? a_elems * 2 : fmt == MXFP8 ? a_elems : a_elems / 2;
-  const size_t b_bytes = fmt == BF16 ? b_elems * 2 : fmt == MXFP8 ? b_elems : b_elems / 2;
+  const size_t a_bytes = fmt == FP64 ? a_elems * 8 : fmt == BF16 ? a_elems * 2 : fmt == MXFP8 ? a_elems : a_elems / 2;
+  const size_t b_bytes = fmt == FP64 ? b_elems * 8 : fmt == BF16 ? b_elems * 2 : fmt == MXFP8 ? b_elems : b_elems / 2;
+  const size_t sum_size = fmt == FP64 ? 8 : 4;  // of a checksum, an expectation and an element of C
   std::vector<uint16_t> ha, hb;
+  std::vector<uint64_t> da, db;
+  if (fmt == FP64 && !a_file.empty() && !(read_f64(a_file, a_elems, &da) && read_f64(b_file, b_elems, &db)))
+    return usage("gemm: --a/--b must hold exactly M*K and N*K doubles, integers of magnitude <= 65535");
   std::vector<unsigned char> xa, xb, hsa, hsb;
   if (fmt == BF16 && !a_file.empty() && !(read_operand(a_file, a_elems, &ha) && read_operand(b_file, b_elems, &hb)))
     return usage("gemm: --a/--b must hold exactly M*K and N*K bf16 integers in [-2, 2]");
-  if (fmt != BF16 && !a_file.empty() &&
+  if (mx && !a_file.empty() &&
       !(read_mx(a_file, a_bytes, fmt, &xa) && read_mx(b_file, b_bytes, fmt, &xb) &&
         read_mx(sa_file, a_elems / 32, 0, &hsa) && read_mx(sb_file, b_elems / 32, 0, &hsb)))
     return usage("gemm: --a/--b must hold exactly M*K and N*K E4M3 bytes of -2 .. 2 (mxfp8) or E2M1 codes of 0 .. 2 "
@@ -858,22 +1232,24 @@ static int run_gemm(int fmt, int M, int N, int K, uint32_t seed, const std::stri
   GemmResult* res = nullptr;
   CHECK(hipMalloc(&g.A, a_bytes));
   CHECK(hipMalloc(&g.B, b_bytes));
-  if (fmt != BF16) {
+  if (mx) {
     CHECK(hipMalloc(&g.SA, a_elems / 32));
     CHECK(hipMalloc(&g.SB, b_elems / 32));
   }
-  CHECK(hipMalloc(&g.colsum, ncol * 4));
-  CHECK(hipMalloc(&g.rowsum, nrow * 4));
-  CHECK(hipMalloc(&g.colexp, ncol * 4));
-  CHECK(hipMalloc(&g.rowexp, nrow * 4));
+  CHECK(hipMalloc(&g.colsum, ncol * sum_size));
+  CHECK(hipMalloc(&g.rowsum, nrow * sum_size));
+  CHECK(hipMalloc(&g.colexp, ncol * sum_size));
+  CHECK(hipMalloc(&g.rowexp, nrow * sum_size));
   CHECK(hipMalloc(&g.ea, static_cast<size_t>(tiles_m) * K * 4));
   CHECK(hipMalloc(&g.eb, static_cast<size_t>(tiles_n) * K * 4));
   CHECK(hipMalloc(&res, sizeof(GemmResult)));
-  if (!c_out.empty()) CHECK(hipMalloc(&g.C, static_cast<size_t>(M) * N * 4));
+  if (!c_out.empty()) CHECK(hipMalloc(&g.C, static_cast<size_t>(M) * N * sum_size));
   if (!a_file.empty()) {
-    CHECK(hipMemcpy(g.A, fmt == BF16 ? static_cast<const void*>(ha.data()) : xa.data(), a_bytes, hipMemcpyHostToDevice));
-    CHECK(hipMemcpy(g.B, fmt == BF16 ? static_cast<const void*>(hb.data()) : xb.data(), b_bytes, hipMemcpyHostToDevice));
-    if (fmt != BF16) {
+    const void* pa = fmt == FP64 ? static_cast<const void*>(da.data()) : fmt == BF16 ? static_cast<const void*>(ha.data()) : xa.data();
+    const void* pb = fmt == FP64 ? static_cast<const void*>(db.data()) : fmt == BF16 ? static_cast<const void*>(hb.data()) : xb.data();
+    CHECK(hipMemcpy(g.A, pa, a_bytes, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(g.B, pb, b_bytes, hipMemcpyHostToDevice));
+    if (mx) {
       CHECK(hipMemcpy(g.SA, hsa.data(), hsa.size(), hipMemcpyHostToDevice));
       CHECK(hipMemcpy(g.SB, hsb.data(), hsb.size(), hipMemcpyHostToDevice));
     }
@@ -892,10 +1268,15 @@ static int run_gemm(int fmt, int M, int N, int K, uint32_t seed, const std::stri
     CHECK(hipMemset(res, 0, sizeof(GemmResult)));
     if (fmt == BF16) gemm_pass<BF16>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
     else if (fmt == MXFP8) gemm_pass<MXFP8>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
-    else gemm_pass<MXFP4>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
-    // the mxfp4 checksums are compared in quarter-units
-    hipLaunchKernelGGL(verify_kernel, dim3(grid), dim3(256), 0, 0, g.colsum, g.colexp, ncol, N, g.rowsum, g.rowexp, nrow,
-                       M, fmt == MXFP4 ? 4.0f : 1.0f, res);
+    else if (fmt == MXFP4) gemm_pass<MXFP4>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
+    else gemm_pass<FP64>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
+    if (fmt == FP64)
+      hipLaunchKernelGGL(verify_f64_kernel, dim3(grid), dim3(256), 0, 0, reinterpret_cast<const double*>(g.colsum),
+                         reinterpret_cast<const long long*>(g.colexp), ncol, N, reinterpret_cast<const double*>(g.rowsum),
+                         reinterpret_cast<const long long*>(g.rowexp), nrow, M, res);
+    else  // the mxfp4 checksums are compared in quarter-units
+      hipLaunchKernelGGL(verify_kernel, dim3(grid), dim3(256), 0, 0, g.colsum, g.colexp, ncol, N, g.rowsum, g.rowexp, nrow,
+                         M, fmt == MXFP4 ? 4.0f : 1.0f, res);
     hipLaunchKernelGGL(locate_kernel, dim3(1), dim3(1), 0, 0, res, tiles_n);
     CHECK(hipGetLastError());
     CHECK(hipMemcpy(&host, res, sizeof(GemmResult), hipMemcpyDeviceToHost));
@@ -906,10 +1287,10 @@ static int run_gemm(int fmt, int M, int N, int K, uint32_t seed, const std::stri
   } while (host.count == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < seconds);
 
   if (C != nullptr) {
-    std::vector<float> hc(static_cast<size_t>(M) * N);
-    CHECK(hipMemcpy(hc.data(), C, hc.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<unsigned char> hc(static_cast<size_t>(M) * N * sum_size);  // floats, or doubles for fp64
+    CHECK(hipMemcpy(hc.data(), C, hc.size(), hipMemcpyDeviceToHost));
     FILE* f = fopen(c_out.c_str(), "wb");
-    if (!f || fwrite(hc.data(), 4, hc.size(), f) != hc.size()) return usage("gemm: cannot write --c-out");
+    if (!f || fwrite(hc.data(), 1, hc.size(), f) != hc.size()) return usage("gemm: cannot write --c-out");
     fclose(f);
   }
   const bool ok = host.count == 0;
@@ -928,7 +1309,8 @@ static int run_gemm(int fmt, int M, int N, int K, uint32_t seed, const std::stri
   const double tflops = gemm_ms > 0 ? 2.0 * M * N * K * passes / (gemm_ms * 1e-3) / 1e12 : 0.0;
   printf("{\"check\":\"gemm\",%s\"ok\":%s,\"m\":%d,\"n\":%d,\"k\":%d,\"passes\":%d,\"mismatch_count\":%u,\"mismatches\":[%s],"
          "\"tflops\":%.3f}\n",
-         fmt == MXFP8 ? "\"dtype\":\"mxfp8\"," : fmt == MXFP4 ? "\"dtype\":\"mxfp4\"," : "", ok ? "true" : "false", M, N, K,
+         fmt == MXFP8 ? "\"dtype\":\"mxfp8\"," : fmt == MXFP4 ? "\"dtype\":\"mxfp4\"," : fmt == FP64 ? "\"dtype\":\"fp64\"," : "",
+         ok ? "true" : "false", M, N, K,
          passes, host.count, recs.c_str(), tflops);
   return ok ? 0 : 1;
 }
@@ -1023,8 +1405,8 @@ int main(int argc, char** argv) {
     else if (gemm && k == "--sb") sb_file = v;
     else if (gemm && k == "--dtype") {
       const std::string d = v;
-      if (d != "bf16" && d != "mxfp8" && d != "mxfp4") return usage("--dtype wants bf16, mxfp8 or mxfp4");
-      fmt = d == "bf16" ? BF16 : d == "mxfp8" ? MXFP8 : MXFP4;
+      if (d != "bf16" && d != "mxfp8" && d != "mxfp4" && d != "fp64") return usage("--dtype wants bf16, mxfp8, mxfp4 or fp64");
+      fmt = d == "bf16" ? BF16 : d == "mxfp8" ? MXFP8 : d == "mxfp4" ? MXFP4 : FP64;
     }
     else if (gemm && k == "--c-out") c_out = v;
     else if (gemm && k == "--seconds") seconds = atof(v);
@@ -1046,7 +1428,7 @@ int main(int argc, char** argv) {
     } else return usage(("unknown option " + k).c_str());
   }
   if (device < 0) return usage("--device must not be negative");
-  if (K == 0) K = fmt == BF16 ? 4096 : fmt == MXFP8 ? 8192 : 2048;  // the default: for the mx types the format's cap
+  if (K == 0) K = fmt == BF16 || fmt == FP64 ? 4096 : fmt == MXFP8 ? 8192 : 2048;  // the default: for the mx types the format's cap
   if (mode == "gemm")
     return run_gemm(fmt, M, N, K, seed, a_file, b_file, sa_file, sb_file, c_out, poison_i, poison_j, device, seconds);
   return run_hbm(mib, passes, seed, flip, flip_word, flip_mask, device);

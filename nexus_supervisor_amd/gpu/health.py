@@ -4,7 +4,9 @@ Telemetry reads what amd-smi counted; this asks the device itself.  ``bin/gpu_ch
 (``csrc/health/gpu_check.hip``) runs a known-answer bf16 GEMM on the matrix units, checked
 exactly by on-device checksums, and a moving-inversions sweep over HBM.  Both answers are
 exact: pass and fail need no tolerance.  On request the same GEMM check also runs in the
-microscaling formats (MXFP8, MXFP4) on the scaled matrix path, which the bf16 one never touches.
+microscaling formats (MXFP8, MXFP4) on the scaled matrix path, which the bf16 one never touches,
+and in FP64 on the double-precision matrix path (``v_mfma_f64_16x16x4_f64``), where a 53-bit
+significand leaves room for wide data: random 17-bit signed integers, not five small values.
 
 The checks run as child processes, one after the other.  The caller (a long-lived agent)
 never opens the GPU itself, so it never shows in amd-smi's process list, and a child that
@@ -49,6 +51,8 @@ def _run_step(cmd: List[str], timeout: float) -> Tuple[Dict[str, Any], Optional[
 # the largest K at which the binary's exactness argument holds, per microscaling format
 # (``run_gemm`` in csrc/health/gpu_check.hip enforces the same)
 MX_K_CAP = {"mxfp8": 8192, "mxfp4": 2048}
+# the same for every format that adds a child to the bf16 one
+EXTRA_K_CAP = {**MX_K_CAP, "fp64": 8192}
 
 
 def check_gpu(device: int = 0, *, gemm: Sequence[int] = (8192, 8192, 4096), seconds: float = 2.0,
@@ -57,14 +61,15 @@ def check_gpu(device: int = 0, *, gemm: Sequence[int] = (8192, 8192, 4096), seco
     """Run the GEMM check, then the HBM check, on ``device``.  ``hbm_mib=None`` lets the
     binary size the sweep (the smaller of 32 GiB and half of what is free); ``binary``
     overrides the built ``bin/gpu_check``.  ``dtypes`` names the GEMM formats: ``"bf16"``
-    always, and each of ``"mxfp8"``, ``"mxfp4"`` adds one child after it with the same M and N
-    and K capped at ``MX_K_CAP``, its record under ``"gemm_mxfp8"`` / ``"gemm_mxfp4"``.  Returns
+    always, and each of ``"mxfp8"``, ``"mxfp4"``, ``"fp64"`` adds one child after it (the FP64
+    one after the microscaling ones) with the same M and N and K capped at ``EXTRA_K_CAP``,
+    its record under ``"gemm_mxfp8"`` / ``"gemm_mxfp4"`` / ``"gemm_fp64"``.  Returns
     ``{"ok", "device", "gemm", "hbm", "elapsed_s", "error"}`` and those: ``ok`` only if every
     child exited 0 and said ok; ``error`` names the steps that failed and how.  After a step
     that ended by signal or timeout nothing more is started: the rest is ``{"skipped": True}``."""
-    extra = [d for d in dtypes if d != "bf16"]
-    if "bf16" not in dtypes or any(d not in MX_K_CAP for d in extra) or len(set(dtypes)) != len(dtypes):
-        raise ValueError(f"dtypes must be 'bf16' and any of {sorted(MX_K_CAP)}, each once: {tuple(dtypes)!r}")
+    if "bf16" not in dtypes or any(d != "bf16" and d not in EXTRA_K_CAP for d in dtypes) or len(set(dtypes)) != len(dtypes):
+        raise ValueError(f"dtypes must be 'bf16' and any of {sorted(EXTRA_K_CAP)}, each once: {tuple(dtypes)!r}")
+    extra = [d for d in dtypes if d in MX_K_CAP] + [d for d in dtypes if d == "fp64"]  # fp64 after the mx ones
     if binary is None:
         from .. import _build
 
@@ -73,7 +78,7 @@ def check_gpu(device: int = 0, *, gemm: Sequence[int] = (8192, 8192, 4096), seco
     steps = [
         ("gemm", [binary, "gemm", "--m", str(m), "--n", str(n), "--k", str(k), "--seconds", repr(float(seconds)),
                   "--device", str(device)]),
-        *((f"gemm_{d}", [binary, "gemm", "--dtype", d, "--m", str(m), "--n", str(n), "--k", str(min(k, MX_K_CAP[d])),
+        *((f"gemm_{d}", [binary, "gemm", "--dtype", d, "--m", str(m), "--n", str(n), "--k", str(min(k, EXTRA_K_CAP[d])),
                          "--seconds", repr(float(seconds)), "--device", str(device)]) for d in extra),
         ("hbm", [binary, "hbm", "--passes", str(passes), "--device", str(device)]
          + (["--mib", repr(float(hbm_mib))] if hbm_mib is not None else [])),
@@ -129,7 +134,7 @@ def summarize(result: Dict[str, Any]) -> str:
     """The one-line cause text an operator sees, e.g.
     ``gpu 0: gemm mismatch at C[37,101] (+1) in tile 0; hbm clean``."""
     parts = [_gemm_text(result.get("gemm") or {})]
-    parts += [_gemm_text(result[f"gemm_{d}"] or {}, f"gemm {d}") for d in MX_K_CAP if f"gemm_{d}" in result]
+    parts += [_gemm_text(result[f"gemm_{d}"] or {}, f"gemm {d}") for d in EXTRA_K_CAP if f"gemm_{d}" in result]
     text = f"gpu {result.get('device')}: {'; '.join(parts)}; {_hbm_text(result.get('hbm') or {})}"
     # "wrong data" is already told by the mismatch; a crash, a timeout or bad output is not
     other = [e for e in (result.get("error") or "").split("; ") if e and not e.endswith(": wrong data")]
