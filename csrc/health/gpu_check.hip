@@ -39,6 +39,23 @@
 //        loads, compares with what the pass before wrote and stores the next pattern (odd
 //        passes store the bitwise complement, so every cell is held in both states); a last
 //        read-only sweep checks what the final pass wrote.
+//   gpu_check cu [--k K] [--reps R] [--passes P] [--rounds N] [--seed S]
+//                [--flip WG:WORD:MASK] [--poison WG:WAVE:I,J] [--device D]
+//        *where on the die*: one workgroup per compute unit, each holding the CU's whole 160 KB of
+//        LDS so that no two share a CU.  Every wave reads the hardware-ID status registers, and
+//        the workgroup reports per physical CU (XCC, SE, SH, CU) and SIMD.  It runs the moving
+//        inversions of `hbm` over all 40960 words of the CU's LDS (--passes, default 4), then on
+//        each of its 16 waves a chain of K / 16 v_mfma_f32_32x32x16_bf16 (--k, a multiple of 16,
+//        at most and by default 304: what the operands of 16 waves take of the LDS) from zeroed
+//        accumulators, --reps times (default 16), each compared with == against the same dot
+//        products in 32-bit integer arithmetic on the same LDS operands: integers in [-2, 2], a
+//        sum of magnitude <= 4 K, exact in fp32.  One launch is a round; the dispatcher may reuse
+//        a CU that has just become free, so up to --rounds (default 8) are launched until every
+//        CU and every SIMD of it has been seen.  A check that did not reach a CU has not cleared
+//        it: incomplete coverage is exit 1 with "error":"coverage".  The verdict needs an
+//        otherwise idle device.  --flip xors one LDS word of workgroup WG after the first write
+//        pass, --poison adds 1 to element I,J of one wave's block after its first chain, both in
+//        round 0 only.
 //
 // The last stdout line is one JSON object.  Exit 0: every check passed; 1: wrong data found;
 // 2: usage error; 3: a HIP call failed.  --poison and --flip are the detectors' self-tests:
@@ -1060,6 +1077,230 @@ __global__ __launch_bounds__(256) void hbm_sweep_kernel(u32x4* __restrict__ p, s
 }
 
 // ------------------------------------------------------------------------------------------
+// Per CU: the whole LDS as memory, then a known-answer matrix chain on every SIMD
+// ------------------------------------------------------------------------------------------
+
+constexpr int CU_WAVES = 16;                       // per workgroup: four per SIMD when spread evenly
+constexpr int CU_THREADS = CU_WAVES * 64;
+constexpr int CU_LDS_BYTES = 163840;               // all of a CU's LDS: no second workgroup fits beside this one
+constexpr int CU_LDS_WORDS = CU_LDS_BYTES / 4;     // 40960
+constexpr int CU_LDS_CHUNKS = CU_LDS_BYTES / 16;   // 10240, ten per thread and sweep
+constexpr int CU_K_CAP = 304;                      // 256 rows x (2 * 304 + 16) B = 159744 B <= 163840 B
+constexpr int CU_PITCH = CU_K_CAP * 2 + 16;        // 624 B: an operand row and its pad
+constexpr int CU_ROWS = 256;                       // four 32-row panels of A, then four of B
+constexpr int CU_NOT_INT = INT32_MIN;              // the delta of an accumulator that holds no integer
+
+// s_getreg operand: (size - 1) << 11 | offset << 6 | register.  Both are reads of status registers.
+constexpr int CU_GETREG_HW_ID = (31 << 11) | 4;    // HW_REG_HW_ID, all 32 bits
+constexpr int CU_GETREG_XCC_ID = (3 << 11) | 20;   // HW_REG_XCC_ID, bits 3:0
+
+struct CuWave {  // what one wave saw; the host puts the sixteen of a workgroup together
+  uint32_t hw_id, xcc_id;
+  uint32_t lds_count, lds_offset, lds_expected, lds_got;  // mismatching words; one of them
+  uint32_t mfma_count;                                    // mismatching accumulator elements; one of them
+  int mfma_i, mfma_j, mfma_delta;
+};
+struct CuResult {
+  CuWave wave[CU_WAVES];
+};
+struct CuArgs {
+  uint32_t seed;
+  int passes, K, reps;
+  int flip_wg, flip_word;  // flip_wg, poison_wg < 0: none
+  uint32_t flip_mask;
+  int poison_wg, poison_wave, poison_i, poison_j;
+};
+
+// What pass `pass` leaves in LDS word `word` of workgroup `wg`: as hbm_pattern, a hash of the
+// address, complemented on odd passes.
+__host__ __device__ static inline uint32_t lds_pattern(uint32_t seed, uint32_t wg, uint32_t word, uint32_t pass) {
+  const uint32_t h = mix32(seed ^ (mix32(wg + (pass >> 1) * 0x9e3779b9u) + word));
+  return (pass & 1u) ? ~h : h;
+}
+
+// The integer side's view of an operand and of an accumulator: decoded from the bit pattern
+// with integer operations, never a conversion (as f64_int above).  An operand is 0, +-1
+// (exponent 127) or +-2 (128).
+__device__ static inline int bf16_small_int(uint32_t bits16) {
+  const int e = (bits16 >> 7) & 0xff, mag = e ? 1 << ((e - 127) & 31) : 0;
+  return (bits16 & 0x8000u) ? -mag : mag;
+}
+
+// False when the float holds no integer of magnitude below 2^24: a fraction, an infinity, a NaN.
+__device__ static inline bool f32_int(uint32_t bits, int* out) {
+  const int e = (bits >> 23) & 0xff;
+  const uint32_t frac = bits & 0x7fffffu;
+  *out = 0;
+  if (e == 0) return frac == 0;          // +-0; a subnormal is a fraction
+  if (e < 127 || e > 150) return false;  // below 1; 2^24 and above, infinity, NaN
+  const uint32_t sig = 0x800000u | frac;  // the value is sig * 2^(e - 150)
+  const int drop = 150 - e;               // 0 .. 23
+  if (sig & ((1u << drop) - 1u)) return false;
+  const int mag = static_cast<int>(sig >> drop);
+  *out = (bits >> 31) ? -mag : mag;
+  return true;
+}
+
+// Compiled for gfx950 (-O3, kernel-resource-usage): 92 VGPRs + 0 AGPRs, 163840 B LDS, 0 scratch,
+// 0 SGPR/VGPR spills; occupancy 4 waves per SIMD, which is this one workgroup: the LDS admits
+// no second one on the CU.
+//
+// The work split is by hardware unit, not by data.  A workgroup declares all 160 KB of LDS, so
+// it has a CU to itself, and the grid is one workgroup per CU of the device: on an idle device
+// every CU gets one.  No workgroup waits for another.  Its 16 waves are more than the 4 SIMDs;
+// each wave reads HW_REG_HW_ID and HW_REG_XCC_ID (s_getreg_b32, scalar reads of status
+// registers) and reports what it read, so the host sees the CU (XCC, SE, SH, CU) and which
+// SIMD each wave ran on.  HW_ID on this family: wave slot 3:0, SIMD 5:4, pipe 7:6, CU 11:8,
+// SH 12, SE 14:13; XCC_ID 3:0.  The kernel hands the registers over whole; the host decodes.
+//
+// Phase A, LDS as memory: moving inversions over the 10240 16-byte chunks.  Sweep s checks what
+// sweep s-1 wrote and stores pass s (odd passes the complement); sweep `passes` only checks.
+// In sweep s thread t owns chunks 1024 i + ((t + 65 s) & 1023), i = 0..9: one ds_read_b128 and
+// one ds_write_b128 each.  The 64 lanes of a wave touch 64 consecutive chunks (a run that wraps
+// at 1024 keeps chunk mod 16 = (t + 65 s) mod 16), so any 16 lanes served together whose lane
+// numbers are distinct mod 16 (16 consecutive ones, or the sets {0-3, 12-15, 20-23, 24-27} and
+// {4-7, 8-11, 16-19, 28-31} of the FP64 kernel's comment) start in 16 distinct 4-bank groups of
+// the 64 banks: conflict-free.  The step of 65 moves a chunk to the next wave (for most
+// placements another SIMD) and the next lane each sweep, so no cell is always written and read
+// through the same lane; a barrier separates the sweeps.
+//
+// Phase B, the matrix unit of each SIMD: the workgroup regenerates operands in the LDS it has
+// just verified, integers in [-2, 2] as bf16 from the hash of the GEMM inputs: four 32 x K_CAP
+// panels of A and four of B.  Wave w owns the 32x32 block (w / 4, w % 4): A panel w / 4 against
+// B panel w % 4, sixteen different blocks from eight panels, which is what lets K reach 304 (a
+// panel pair per wave would stop at 128).  The chain is K / 16 v_mfma_f32_32x32x16_bf16 into
+// one accumulator, `reps` times from zero; lane l reads row (A) or column (B) l % 32 at k
+// 8 * (l / 32) .. + 7 with one ds_read_b128 per operand and instruction.  Rows are *padded* to
+// 624 bytes, 39 chunks: the 16 lanes served together read rows with 16 distinct r mod 16 (in
+// either lane grouping above) at one k offset, chunk 39 r + c, and 39 is odd, so 39 r mod 16
+// takes 16 distinct values: conflict-free.  Padding over a swizzle as in the bf16 GEMM: one
+// multiply-add per address, and the integer side below reads the same rows without undoing an xor.
+//
+// The expected block comes from the same LDS operands in 32-bit integer VALU arithmetic: each
+// lane forms the 16 dot products of its accumulator elements (register r of lane l is
+// D[8 * (r / 4) + 4 * (l / 32) + r % 4][l % 32]) once, decoding bf16 by shifts, and after every
+// chain decodes its 16 floats to integers by their bit patterns and compares with ==.  No
+// floating-point instruction is on that side.  |a b| <= 4, so a partial sum is an integer of
+// magnitude <= 4 K <= 1216, far below 2^24: fp32 holds it exactly in any order.
+__global__ __launch_bounds__(CU_THREADS) void cu_check_kernel(CuResult* __restrict__ res, CuArgs a) {
+  __shared__ __attribute__((aligned(16))) u32x4 lds[CU_LDS_CHUNKS];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const uint32_t wg = blockIdx.x;
+  const uint32_t hw_id = __builtin_amdgcn_s_getreg(CU_GETREG_HW_ID);
+  const uint32_t xcc_id = __builtin_amdgcn_s_getreg(CU_GETREG_XCC_ID);
+
+  // ---- phase A
+  uint32_t bad = 0, bad_word = 0, bad_want = 0, bad_got = 0;
+  for (int s = 0; s <= a.passes; ++s) {
+    const int slot = (t + 65 * s) & (CU_THREADS - 1);
+    for (int i = 0; i < CU_LDS_CHUNKS / CU_THREADS; ++i) {
+      const int c = i * CU_THREADS + slot;
+      if (s > 0) {
+        const u32x4 got = lds[c];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const uint32_t want = lds_pattern(a.seed, wg, 4 * c + e, static_cast<uint32_t>(s - 1));
+          if (got[e] != want) {
+            if (bad == 0) bad_word = 4 * c + e, bad_want = want, bad_got = got[e];
+            ++bad;
+          }
+        }
+      }
+      if (s < a.passes) {
+        u32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = lds_pattern(a.seed, wg, 4 * c + e, static_cast<uint32_t>(s));
+        lds[c] = v;
+      }
+    }
+    __syncthreads();
+    if (s == 0 && a.flip_wg == static_cast<int>(wg)) {  // detector self-test: one word changed between two sweeps
+      if (t == 0 && a.flip_word >= 0 && a.flip_word < CU_LDS_WORDS)
+        reinterpret_cast<uint32_t*>(lds)[a.flip_word] ^= a.flip_mask;
+      __syncthreads();
+    }
+  }
+
+  // ---- phase B: operands; row r of the 256 is row r % 32 of panel r / 32
+  unsigned char* const base = reinterpret_cast<unsigned char*>(lds);
+  const uint32_t gs = mix32(a.seed + wg * 0x9e3779b9u);
+  for (int c = t; c < CU_ROWS * (CU_K_CAP / 8); c += CU_THREADS) {
+    const uint32_t row = c / (CU_K_CAP / 8), col = c % (CU_K_CAP / 8) * 8;
+    u32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      v[e] = small_int_bf16(gs, row, col + 2 * e) | (small_int_bf16(gs, row, col + 2 * e + 1) << 16);
+    *reinterpret_cast<u32x4*>(base + row * CU_PITCH + col * 2) = v;
+  }
+  __syncthreads();  // from here LDS is only read
+
+  const int wm = w >> 2, wn = w & 3, l32 = lane & 31, half = lane >> 5;
+  const unsigned char* const pa = base + wm * 32 * CU_PITCH;                   // this wave's panel of A
+  const unsigned char* const pb = base + (128 + wn * 32 + l32) * CU_PITCH;     // this lane's column of B
+  int want[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) want[r] = 0;
+  for (int c8 = 0; c8 < a.K / 8; ++c8) {
+    const u32x4 bv = *reinterpret_cast<const u32x4*>(pb + c8 * 16);
+    int b[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) b[2 * e] = bf16_small_int(bv[e] & 0xffffu), b[2 * e + 1] = bf16_small_int(bv[e] >> 16);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const u32x4 av = *reinterpret_cast<const u32x4*>(pa + (8 * (r >> 2) + 4 * half + (r & 3)) * CU_PITCH + c8 * 16);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        want[r] += bf16_small_int(av[e] & 0xffffu) * b[2 * e] + bf16_small_int(av[e] >> 16) * b[2 * e + 1];
+    }
+  }
+
+  const unsigned char* const sa = pa + l32 * CU_PITCH + half * 16;
+  const unsigned char* const sb = pb + half * 16;
+  const bool poison = a.poison_wg == static_cast<int>(wg) && a.poison_wave == w && a.poison_j == l32;
+  uint32_t mbad = 0;
+  int mbad_i = 0, mbad_delta = 0;
+  for (int rep = 0; rep < a.reps; ++rep) {
+    asm volatile("" ::: "memory");  // every chain reads its operands again
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    for (int kk = 0; kk < a.K / 16; ++kk)
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(sa + kk * 32),
+                                                    *reinterpret_cast<const bf16x8*>(sb + kk * 32), acc, 0, 0, 0);
+    if (poison && rep == 0) {  // detector self-test: one element off by one
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] += 8 * (r >> 2) + 4 * half + (r & 3) == a.poison_i ? 1.0f : 0.0f;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      int have;
+      const bool whole = f32_int(__float_as_uint(acc[r]), &have);
+      if (!whole || have != want[r]) {
+        if (mbad == 0) mbad_i = 8 * (r >> 2) + 4 * half + (r & 3), mbad_delta = whole ? have - want[r] : CU_NOT_INT;
+        ++mbad;
+      }
+    }
+  }
+
+  // ---- the wave's record: counts summed over the lanes, the details of its lowest lane that has any
+  const unsigned long long lds_lanes = __ballot(bad != 0), mfma_lanes = __ballot(mbad != 0);
+  const int lds_src = lds_lanes ? __ffsll(lds_lanes) - 1 : 0, mfma_src = mfma_lanes ? __ffsll(mfma_lanes) - 1 : 0;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) bad += __shfl_xor(bad, off), mbad += __shfl_xor(mbad, off);
+  const CuWave rec = {hw_id,
+                      xcc_id,
+                      bad,
+                      4u * __shfl(bad_word, lds_src),
+                      __shfl(bad_want, lds_src),
+                      __shfl(bad_got, lds_src),
+                      mbad,
+                      __shfl(mbad_i, mfma_src),
+                      mfma_src & 31,
+                      __shfl(mbad_delta, mfma_src)};
+  if (lane == 0) res[wg].wave[w] = rec;
+}
+
+// ------------------------------------------------------------------------------------------
 // Host
 // ------------------------------------------------------------------------------------------
 
@@ -1075,7 +1316,9 @@ static int usage(const char* why) {
           "[--a FILE --b FILE [--sa FILE --sb FILE]] [--c-out FILE] [--poison I,J] "
           "[--device D] [--seconds T]\n         fp64: M and N multiples of 16, K a multiple of 4 and at most 8192; --a/--b "
           "hold doubles, integers of magnitude <= 65535\n       gpu_check hbm --mib SIZE [--passes P] [--seed S] [--flip WORD:MASK] "
-          "[--device D]\n",
+          "[--device D]\n       gpu_check cu [--k K] [--reps R] [--passes P] [--rounds N] [--seed S] [--flip WG:WORD:MASK] "
+          "[--poison WG:WAVE:I,J] [--device D]\n         K a multiple of 16 and at most 304, what 16 waves' operands take of "
+          "the 160 KB of LDS; WORD below 40960, WAVE below 16, I,J inside 32x32\n",
           why);
   return 2;
 }
@@ -1377,12 +1620,115 @@ static int run_hbm(double mib, int passes, uint32_t seed, bool flip, unsigned lo
   return ok ? 0 : 1;
 }
 
+struct CuPlace {  // HW_ID and XCC_ID decoded (the layout is in the kernel's comment)
+  int xcc, se, sh, cu, simd;
+  int cu_key() const { return ((xcc * 4 + se) * 2 + sh) * 16 + cu; }
+};
+
+static CuPlace cu_place(const CuWave& w) {
+  return {static_cast<int>(w.xcc_id & 15u), static_cast<int>((w.hw_id >> 13) & 3u), static_cast<int>((w.hw_id >> 12) & 1u),
+          static_cast<int>((w.hw_id >> 8) & 15u), static_cast<int>((w.hw_id >> 4) & 3u)};
+}
+
+static int run_cu(CuArgs a, int rounds, int device) {
+  if (a.K < 16 || a.K % 16 || a.K > CU_K_CAP) return usage("cu: --k must be a multiple of 16, from 16 to 304");
+  if (a.reps < 1 || a.passes < 1 || rounds < 1 || rounds > 64)
+    return usage("cu: --reps and --passes must be at least 1, --rounds from 1 to 64");
+  if (a.flip_wg >= 0 && a.flip_word >= CU_LDS_WORDS) return usage("cu: --flip word outside the 40960 words of LDS");
+  if (a.poison_wg >= 0 && (a.poison_wave >= CU_WAVES || a.poison_i >= 32 || a.poison_j >= 32))
+    return usage("cu: --poison wants a wave below 16 and I,J inside the 32x32 block");
+  CHECK(hipSetDevice(device));
+  hipDeviceProp_t prop;
+  CHECK(hipGetDeviceProperties(&prop, device));
+  const int cus = prop.multiProcessorCount;
+  if (a.flip_wg >= cus || a.poison_wg >= cus) return usage("cu: --flip / --poison workgroup past the device's CUs");
+  CuResult* res = nullptr;
+  const size_t res_bytes = static_cast<size_t>(cus) * sizeof(CuResult);
+  CHECK(hipMalloc(&res, res_bytes));
+  hipEvent_t ev0, ev1;
+  CHECK(hipEventCreate(&ev0));
+  CHECK(hipEventCreate(&ev1));
+
+  std::vector<CuResult> host(cus);
+  std::vector<bool> seen_cu(8192, false), seen_simd(4 * 8192, false);
+  int covered = 0, simds = 0, done = 0, nbad = 0;
+  double ms_total = 0.0;
+  std::string bad, placement;
+  const CuArgs first = a;
+  for (int round = 0; round < rounds && (covered < cus || simds < 4 * cus); ++round) {
+    a = first;
+    a.seed = first.seed + static_cast<uint32_t>(round);
+    if (round > 0) a.flip_wg = a.poison_wg = -1;  // the self-tests alter round 0 only
+    CHECK(hipMemset(res, 0, res_bytes));
+    CHECK(hipEventRecord(ev0));
+    hipLaunchKernelGGL(cu_check_kernel, dim3(cus), dim3(CU_THREADS), 0, 0, res, a);
+    CHECK(hipEventRecord(ev1));
+    CHECK(hipGetLastError());
+    CHECK(hipMemcpy(host.data(), res, res_bytes, hipMemcpyDeviceToHost));
+    float ms = 0.0f;
+    CHECK(hipEventElapsedTime(&ms, ev0, ev1));
+    ms_total += ms;
+    ++done;
+    int spread[5] = {0, 0, 0, 0, 0}, strays = 0;  // workgroups by the number of SIMDs their waves ran on
+    int fewest = CU_WAVES, most = 0;              // waves of one workgroup on one SIMD
+    for (int wg = 0; wg < cus; ++wg) {
+      const CuWave* w = host[wg].wave;
+      const CuPlace at = cu_place(w[0]);
+      unsigned long long lds_count = 0, mfma_count = 0;
+      int lds_w = -1, mfma_w = -1, mask = 0, on[4] = {0, 0, 0, 0};
+      for (int x = 0; x < CU_WAVES; ++x) {
+        const CuPlace p = cu_place(w[x]);
+        strays += p.cu_key() != at.cu_key();  // a workgroup's waves share a CU: anything else is a wrong decode
+        mask |= 1 << p.simd;
+        ++on[p.simd];
+        if (!seen_cu[p.cu_key()]) seen_cu[p.cu_key()] = true, ++covered;
+        if (!seen_simd[p.cu_key() * 4 + p.simd]) seen_simd[p.cu_key() * 4 + p.simd] = true, ++simds;
+        lds_count += w[x].lds_count;
+        mfma_count += w[x].mfma_count;
+        if (w[x].lds_count && (lds_w < 0 || w[x].lds_offset < w[lds_w].lds_offset)) lds_w = x;
+        if (w[x].mfma_count && mfma_w < 0) mfma_w = x;
+      }
+      ++spread[__builtin_popcount(mask)];
+      fewest = std::min(fewest, *std::min_element(on, on + 4));
+      most = std::max(most, *std::max_element(on, on + 4));
+      if (lds_w < 0 && mfma_w < 0) continue;
+      if (nbad++ >= MAX_RECORDS) continue;
+      char buf[400];
+      int n = snprintf(buf, sizeof buf, "%s{\"xcc\":%d,\"se\":%d,\"sh\":%d,\"cu\":%d,\"wg\":%d,\"round\":%d", nbad > 1 ? "," : "",
+                       at.xcc, at.se, at.sh, at.cu, wg, round);
+      if (lds_w >= 0)
+        n += snprintf(buf + n, sizeof buf - n, ",\"lds\":{\"count\":%llu,\"offset\":%u,\"expected\":%u,\"got\":%u,\"xor\":%u}",
+                      lds_count, w[lds_w].lds_offset, w[lds_w].lds_expected, w[lds_w].lds_got,
+                      w[lds_w].lds_expected ^ w[lds_w].lds_got);
+      if (mfma_w >= 0)
+        n += snprintf(buf + n, sizeof buf - n, ",\"mfma\":{\"count\":%llu,\"simd\":%d,\"i\":%d,\"j\":%d,\"delta\":%d}", mfma_count,
+                      cu_place(w[mfma_w]).simd, w[mfma_w].mfma_i, w[mfma_w].mfma_j, w[mfma_w].mfma_delta);
+      bad += std::string(buf) + "}";
+    }
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s{\"round\":%d,\"ms\":%.3f,\"covered\":%d,\"simds\":%d,\"wgs_on_1_2_3_4_simds\":[%d,%d,%d,%d],"
+             "\"waves_per_simd\":[%d,%d],\"strays\":%d}",
+             round ? "," : "", round, ms, covered, simds, spread[1], spread[2], spread[3], spread[4], fewest, most, strays);
+    placement += buf;
+  }
+  CHECK(hipFree(res));
+  const bool reached = covered == cus && simds == 4 * cus;
+  const bool ok = reached && nbad == 0;
+  printf("{\"check\":\"cu\",\"ok\":%s,%s\"cus\":%d,\"covered\":%d,\"simds\":%d,\"rounds\":%d,\"k\":%d,\"reps\":%d,\"passes\":%d,"
+         "\"lds_bytes\":%d,\"bad_count\":%d,\"bad\":[%s],\"placement\":[%s],\"ms\":%.3f}\n",
+         ok ? "true" : "false", reached ? "" : "\"error\":\"coverage\",", cus, covered, simds, done, first.K, first.reps,
+         first.passes, CU_LDS_BYTES, nbad, bad.c_str(), placement.c_str(), ms_total);
+  return ok ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return usage("a subcommand is needed");
   const std::string mode = argv[1];
-  if (mode != "gemm" && mode != "hbm") return usage("unknown subcommand");
-  g_check = mode == "gemm" ? "gemm" : "hbm";
-  int fmt = BF16, M = 8192, N = 8192, K = 0, device = 0, passes = 2, poison_i = -1, poison_j = -1;
+  if (mode != "gemm" && mode != "hbm" && mode != "cu") return usage("unknown subcommand");
+  g_check = mode == "gemm" ? "gemm" : mode == "hbm" ? "hbm" : "cu";
+  const bool cu = mode == "cu";
+  int fmt = BF16, M = 8192, N = 8192, K = 0, device = 0, passes = cu ? 4 : 2, poison_i = -1, poison_j = -1;
+  int reps = 16, rounds = 8, flip_wg = -1, poison_wg = -1, poison_wave = 0;  // cu only
   double seconds = 2.0, mib = 0.0;
   uint32_t seed = 1, flip_mask = 0;
   unsigned long long flip_word = 0;
@@ -1396,9 +1742,28 @@ int main(int argc, char** argv) {
     const bool gemm = mode == "gemm";
     if (k == "--device") device = atoi(v);
     else if (k == "--seed") seed = static_cast<uint32_t>(strtoul(v, nullptr, 0));
+    else if (cu && k == "--reps") reps = atoi(v);
+    else if (cu && k == "--rounds") rounds = atoi(v);
+    else if (cu && k == "--flip") {
+      flip_wg = static_cast<int>(strtol(v, &end, 0));
+      if (*end != ':' || flip_wg < 0) return usage("--flip wants WG:WORD:MASK");
+      flip_word = strtoull(end + 1, &end, 0);
+      if (*end != ':') return usage("--flip wants WG:WORD:MASK");
+      flip_mask = static_cast<uint32_t>(strtoul(end + 1, &end, 0));
+      if (*end != '\0' || flip_mask == 0) return usage("--flip wants WG:WORD:MASK with a non-zero mask");
+    } else if (cu && k == "--poison") {
+      poison_wg = static_cast<int>(strtol(v, &end, 10));
+      if (*end != ':' || poison_wg < 0) return usage("--poison wants WG:WAVE:I,J");
+      poison_wave = static_cast<int>(strtol(end + 1, &end, 10));
+      if (*end != ':' || poison_wave < 0) return usage("--poison wants WG:WAVE:I,J");
+      poison_i = static_cast<int>(strtol(end + 1, &end, 10));
+      if (*end != ',' || poison_i < 0) return usage("--poison wants WG:WAVE:I,J");
+      poison_j = static_cast<int>(strtol(end + 1, &end, 10));
+      if (*end != '\0' || poison_j < 0) return usage("--poison wants WG:WAVE:I,J");
+    }
     else if (gemm && k == "--m") M = atoi(v);
     else if (gemm && k == "--n") N = atoi(v);
-    else if (gemm && k == "--k") K = atoi(v);
+    else if ((gemm || cu) && k == "--k") K = atoi(v);
     else if (gemm && k == "--a") a_file = v;
     else if (gemm && k == "--b") b_file = v;
     else if (gemm && k == "--sa") sa_file = v;
@@ -1415,11 +1780,11 @@ int main(int argc, char** argv) {
       if (*end != ',' || poison_i < 0) return usage("--poison wants I,J");
       poison_j = static_cast<int>(strtol(end + 1, &end, 10));
       if (*end != '\0' || poison_j < 0) return usage("--poison wants I,J");
-    } else if (!gemm && k == "--mib") {
+    } else if (!gemm && !cu && k == "--mib") {
       mib = atof(v);
       if (!(mib > 0)) return usage("--mib must be positive");
     } else if (!gemm && k == "--passes") passes = atoi(v);
-    else if (!gemm && k == "--flip") {
+    else if (!gemm && !cu && k == "--flip") {
       flip_word = strtoull(v, &end, 0);
       if (*end != ':') return usage("--flip wants WORD:MASK");
       flip_mask = static_cast<uint32_t>(strtoul(end + 1, &end, 0));
@@ -1428,7 +1793,13 @@ int main(int argc, char** argv) {
     } else return usage(("unknown option " + k).c_str());
   }
   if (device < 0) return usage("--device must not be negative");
-  if (K == 0) K = fmt == BF16 || fmt == FP64 ? 4096 : fmt == MXFP8 ? 8192 : 2048;  // the default: for the mx types the format's cap
+  if (cu) {
+    flip_word = std::min(flip_word, static_cast<unsigned long long>(CU_LDS_WORDS));  // a word past the LDS is refused below
+    const CuArgs a = {seed,      passes,    K == 0 ? CU_K_CAP : K, reps,    flip_wg, static_cast<int>(flip_word),
+                      flip_mask, poison_wg, poison_wave,           poison_i, poison_j};  // the default K is the cap
+    return run_cu(a, rounds, device);
+  }
+  if (K == 0) K =fmt == BF16 || fmt == FP64 ? 4096 : fmt == MXFP8 ? 8192 : 2048;  // the default: for the mx types the format's cap
   if (mode == "gemm")
     return run_gemm(fmt, M, N, K, seed, a_file, b_file, sa_file, sb_file, c_out, poison_i, poison_j, device, seconds);
   return run_hbm(mib, passes, seed, flip, flip_word, flip_mask, device);

@@ -10,7 +10,7 @@
 ``build``       build the native components in-tree
 ``cqlsrv``      run the native in-memory CQL server (tests / local runs)
 ``gpu-check``   ask one GPU whether it is bad: known-answer MFMA GEMM + HBM pattern test
-                (``--device D``, ``--quick``, ``--json``; exit 1 when a check fails)
+                (``--device D``, ``--quick``, ``--per-cu``, ``--json``; exit 1 when a check fails)
 ``version``     print the version
 """
 from __future__ import annotations
@@ -83,11 +83,12 @@ def main(argv=None) -> int:
         ap.add_argument("--json", action="store_true", help="print the whole record")
         ap.add_argument("--dtypes", default="bf16", help="GEMM formats, comma-separated: bf16[,mxfp8][,mxfp4][,fp64]")
         ap.add_argument("--all-formats", action="store_true", help="the same as --dtypes bf16,mxfp8,mxfp4; for FP64 name it: --dtypes bf16,fp64")
+        ap.add_argument("--per-cu", action="store_true", help="also check every CU's LDS and matrix units, named by XCC, SE and CU")
         a = ap.parse_args(argv)
         quick = {"gemm": (1024, 1024, 1024), "seconds": 0.0, "hbm_mib": 256.0} if a.quick else {}
         dtypes = ("bf16", "mxfp8", "mxfp4") if a.all_formats else tuple(a.dtypes.split(","))
         try:
-            result = check_gpu(a.device, dtypes=dtypes, **quick)
+            result = check_gpu(a.device, dtypes=dtypes, cu=a.per_cu, **quick)
         except ValueError as e:
             ap.error(str(e))
         print(json.dumps(result) if a.json else summarize(result))

@@ -7,6 +7,9 @@ exact: pass and fail need no tolerance.  On request the same GEMM check also run
 microscaling formats (MXFP8, MXFP4) on the scaled matrix path, which the bf16 one never touches,
 and in FP64 on the double-precision matrix path (``v_mfma_f64_16x16x4_f64``), where a 53-bit
 significand leaves room for wide data: random 17-bit signed integers, not five small values.
+Also on request, ``gpu_check cu`` says where on the die: one workgroup per compute unit sweeps that
+CU's whole 160 KB of LDS and runs a known-answer matrix chain on each of its SIMDs, and a fault is
+named by XCC, shader engine and CU, which in CPX mode is one partition and not the whole OAM.
 
 The checks run as child processes, one after the other.  The caller (a long-lived agent)
 never opens the GPU itself, so it never shows in amd-smi's process list, and a child that
@@ -57,13 +60,15 @@ EXTRA_K_CAP = {**MX_K_CAP, "fp64": 8192}
 
 def check_gpu(device: int = 0, *, gemm: Sequence[int] = (8192, 8192, 4096), seconds: float = 2.0,
               hbm_mib: Optional[float] = None, passes: int = 2, timeout: float = 120.0,
-              binary: Optional[str] = None, dtypes: Sequence[str] = ("bf16",)) -> Dict[str, Any]:
+              binary: Optional[str] = None, dtypes: Sequence[str] = ("bf16",), cu: bool = False) -> Dict[str, Any]:
     """Run the GEMM check, then the HBM check, on ``device``.  ``hbm_mib=None`` lets the
     binary size the sweep (the smaller of 32 GiB and half of what is free); ``binary``
     overrides the built ``bin/gpu_check``.  ``dtypes`` names the GEMM formats: ``"bf16"``
     always, and each of ``"mxfp8"``, ``"mxfp4"``, ``"fp64"`` adds one child after it (the FP64
     one after the microscaling ones) with the same M and N and K capped at ``EXTRA_K_CAP``,
-    its record under ``"gemm_mxfp8"`` / ``"gemm_mxfp4"`` / ``"gemm_fp64"``.  Returns
+    its record under ``"gemm_mxfp8"`` / ``"gemm_mxfp4"`` / ``"gemm_fp64"``.  ``cu=True`` adds the
+    per-CU check (``gpu_check cu``: each compute unit's whole LDS and the matrix unit of each of
+    its SIMDs, named by XCC, SE and CU) after the GEMM children, its record under ``"cu"``.  Returns
     ``{"ok", "device", "gemm", "hbm", "elapsed_s", "error"}`` and those: ``ok`` only if every
     child exited 0 and said ok; ``error`` names the steps that failed and how.  After a step
     that ended by signal or timeout nothing more is started: the rest is ``{"skipped": True}``."""
@@ -80,10 +85,12 @@ def check_gpu(device: int = 0, *, gemm: Sequence[int] = (8192, 8192, 4096), seco
                   "--device", str(device)]),
         *((f"gemm_{d}", [binary, "gemm", "--dtype", d, "--m", str(m), "--n", str(n), "--k", str(min(k, EXTRA_K_CAP[d])),
                          "--seconds", repr(float(seconds)), "--device", str(device)]) for d in extra),
+        *([("cu", [binary, "cu", "--device", str(device)])] if cu else []),
         ("hbm", [binary, "hbm", "--passes", str(passes), "--device", str(device)]
          + (["--mib", repr(float(hbm_mib))] if hbm_mib is not None else [])),
     ]
-    out: Dict[str, Any] = {"ok": True, "device": device, "gemm": {}, **{f"gemm_{d}": {} for d in extra}, "hbm": {},
+    out: Dict[str, Any] = {"ok": True, "device": device, "gemm": {}, **{f"gemm_{d}": {} for d in extra},
+                           **({"cu": {}} if cu else {}), "hbm": {},
                            "elapsed_s": 0.0, "error": None}
     errors = []
     t0 = time.monotonic()
@@ -118,6 +125,32 @@ def _gemm_text(rec: Dict[str, Any], label: str = "gemm") -> str:
     return text + (f" and {len(mm) - 1} more" if len(mm) > 1 else "")
 
 
+def _cu_text(rec: Dict[str, Any]) -> str:
+    if rec.get("skipped"):
+        return "cu not run"
+    if rec.get("ok") is True:
+        return "cu clean"
+    bad = rec.get("bad") or []
+    if not bad:
+        if rec.get("error") != "coverage":
+            return "cu failed"
+        if rec.get("covered") != rec.get("cus"):
+            return f"cu reached {rec.get('covered')} of {rec.get('cus')} CUs"
+        return f"cu reached {rec.get('simds')} of {4 * rec.get('cus', 0)} SIMDs"
+    first = bad[0]
+    what = []
+    if "lds" in first:
+        lds = first["lds"]
+        what.append(f"lds {lds['count']} bad word{'s' if lds['count'] != 1 else ''} at byte {lds['offset']} "
+                    f"(xor {lds['xor']:#010x})")
+    if "mfma" in first:
+        mfma = first["mfma"]
+        what.append(f"matrix unit simd {mfma['simd']} wrong at [{mfma['i']},{mfma['j']}] ({mfma['delta']:+d})")
+    more = rec.get("bad_count", len(bad)) - 1
+    return (f"cu xcc {first.get('xcc')} se {first.get('se')} cu {first.get('cu')}: {', '.join(what)}"
+            + (f" and {more} more" if more > 0 else ""))
+
+
 def _hbm_text(rec: Dict[str, Any]) -> str:
     if rec.get("skipped"):
         return "hbm not run"
@@ -135,6 +168,8 @@ def summarize(result: Dict[str, Any]) -> str:
     ``gpu 0: gemm mismatch at C[37,101] (+1) in tile 0; hbm clean``."""
     parts = [_gemm_text(result.get("gemm") or {})]
     parts += [_gemm_text(result[f"gemm_{d}"] or {}, f"gemm {d}") for d in EXTRA_K_CAP if f"gemm_{d}" in result]
+    if "cu" in result:
+        parts.append(_cu_text(result["cu"] or {}))
     text = f"gpu {result.get('device')}: {'; '.join(parts)}; {_hbm_text(result.get('hbm') or {})}"
     # "wrong data" is already told by the mismatch; a crash, a timeout or bad output is not
     other = [e for e in (result.get("error") or "").split("; ") if e and not e.endswith(": wrong data")]
