@@ -1,6 +1,6 @@
 // gpu_check — an active device check with exact answers: "is this GPU bad, or was it the job?"
 //
-//   gpu_check gemm [--dtype bf16|mxfp8|mxfp4|fp64] --m M --n N --k K [--seed S]
+//   gpu_check gemm [--dtype bf16|mxfp8|mxfp4|fp64|int8] --m M --n N --k K [--seed S]
 //                  [--a FILE --b FILE [--sa FILE --sb FILE]] [--c-out FILE]
 //                  [--poison I,J] [--device D] [--seconds T]
 //        bf16 x bf16 -> fp32 GEMM on the matrix units (v_mfma_f32_32x32x16_bf16), checked on
@@ -34,6 +34,15 @@
 //        The expected checksums come from kernels that decode the doubles' bit patterns with
 //        integer operations and add in int64: no instruction of the double-precision unit, a
 //        conversion included, is on that side.
+//        --dtype int8: the same check on the integer matrix path (v_mfma_i32_32x32x32_i8), on
+//        full-range data.  A and B are raw int8 bytes, uniform over all 256 values (-128 among
+//        them) when generated.  Integers need no exactness trick: |element| <= 128, so
+//        |product| <= 2^14 and |C[i][j]| <= 2^14 * K <= 2^30 for K <= 65536, inside int32 whatever
+//        the data (whether the accumulate wraps or saturates past that never arises).  A checksum
+//        over 128 rows or columns is at most 2^37: the epilogue sums the int32 accumulators in
+//        int64, and checksums and expectations are 8 bytes.  M and N are multiples of 32, K a
+//        multiple of 32 and at most 65536.  --a/--b hold M*K and N*K bytes, every byte valid;
+//        --c-out M*N int32.  The expected checksums are plain integer multiply-adds.
 //   gpu_check hbm --mib SIZE [--passes P] [--seed S] [--flip WORD:MASK] [--device D]
 //        moving inversions over one allocation: pass 0 writes an address hash, each later pass
 //        loads, compares with what the pass before wrote and stores the next pattern (odd
@@ -123,7 +132,7 @@ __global__ __launch_bounds__(256) void generate_kernel(uint16_t* __restrict__ x,
 
 // The microscaling inputs, from the same hash.  X is rows x K elements; one thread writes 16
 // bytes: 16 E4M3 bytes, or 32 E2M1 nibbles (one whole scale block).  K is a multiple of 64.
-enum Fmt { BF16 = 0, MXFP8 = 1, MXFP4 = 2, FP64 = 3 };
+enum Fmt { BF16 = 0, MXFP8 = 1, MXFP4 = 2, FP64 = 3, INT8 = 4 };
 
 template <int FMT>
 __device__ static inline uint32_t small_mx_code(uint32_t seed, uint32_t row, uint32_t col) {
@@ -183,6 +192,21 @@ __global__ __launch_bounds__(256) void generate_f64_kernel(uint64_t* __restrict_
     const uint32_t row = static_cast<uint32_t>(c / (K / 2)), col = static_cast<uint32_t>(c % (K / 2)) * 2;
     const u64x2 v = {wide_int_f64(seed, row, col), wide_int_f64(seed, row, col + 1)};
     *reinterpret_cast<u64x2*>(x + c * 2) = v;
+  }
+}
+
+// The INT8 inputs, from the same hash: the low byte of it, so every one of the 256 values occurs,
+// -128 included.  X is rows x K bytes; one thread writes 16 of them.  K is a multiple of 32.
+__global__ __launch_bounds__(256) void generate_i8_kernel(unsigned char* __restrict__ x, int rows, int K, uint32_t seed) {
+  const size_t chunks = static_cast<size_t>(rows) * (K / 16);
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t c = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; c < chunks; c += stride) {
+    const uint32_t row = static_cast<uint32_t>(c / (K / 16)), col = static_cast<uint32_t>(c % (K / 16)) * 16;
+    const uint32_t hr = mix32(seed ^ (row * 0x9e3779b9u));
+    u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int e = 0; e < 16; ++e) v[e / 4] |= (mix32(hr + col + e) & 0xffu) << (e % 4 * 8);
+    *reinterpret_cast<u32x4*>(x + c * 16) = v;
   }
 }
 
@@ -775,6 +799,234 @@ __global__ __launch_bounds__(256, 2) void gemm_abft_f64_kernel(const double* __r
 }
 
 // ------------------------------------------------------------------------------------------
+// The INT8 GEMM on the integer matrix path, with a checksum epilogue in int64
+// ------------------------------------------------------------------------------------------
+
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int I8_TILE_M = 128, I8_TILE_N = 256;  // C tile per workgroup: 2 x 2 waves of 64 x 128
+constexpr int I8_KSTEP = 64;                     // K advance per LDS stage: a stage row is 64 bytes, no padding
+constexpr int I8_CPR = I8_KSTEP / 16;            // 16-byte chunks per stage row, and lanes that copy one
+constexpr int I8_RPS = 256 / I8_CPR;             // rows the 256 threads copy at once
+constexpr int I8_A_BYTES = I8_TILE_M * I8_KSTEP;
+constexpr int I8_STAGE_BYTES = (I8_TILE_M + I8_TILE_N) * I8_KSTEP;
+
+// the xor swizzle of a stage row: chunk c of row r is stored at chunk c ^ i8_key(r)
+__device__ __forceinline__ int i8_key(int r) { return (r >> 2) & (I8_CPR - 1); }
+
+// The checksum epilogue of the INT8 kernel, from registers: a wave holds its 64x128 block as 2x4
+// blocks of 32x32 accumulators, register r of lane l holding D[8 * (r / 4) + 4 * (l / 32) + r % 4][l % 32].
+// Element (bm, bn, r) of this lane is
+//   row  row0 + wm*64 + bm*32 + 8*(r/4) + 4*half + r%4,   column  col0 + wn*128 + bn*32 + l32.
+// An element is at most 2^30 in magnitude and a checksum of 128 of them 2^37, so every sum here
+// is int64.  The stripes stay 128 wide: the column checksums of the workgroup's 128 rows go to
+// stripe tm (two wm partials per column), and a wave's row sums over its four column blocks are
+// already the whole checksum of stripe 2 * tn + wn, which exists only where it starts inside N.
+// `red` is 768 int64 of LDS that no wave reads any more.
+__device__ __forceinline__ void abft_epilogue_i8(i32x16 (&acc)[2][4], long long* red, int M, int N,
+                                                 long long* __restrict__ colsum, long long* __restrict__ rowsum,
+                                                 int* __restrict__ C, int poison_i, int poison_j) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w >> 1, wn = w & 1;
+  const int l32 = lane & 31, half = lane >> 5;
+  const int tn = blockIdx.x, tm = blockIdx.y;
+  const int row0 = tm * I8_TILE_M, col0 = tn * I8_TILE_N;
+  const int lane_row = row0 + wm * 64 + 4 * half, lane_col = col0 + wn * 128 + l32;
+  if (poison_i >= 0) {  // detector self-test: one element off by one
+#pragma unroll
+    for (int bm = 0; bm < 2; ++bm)
+#pragma unroll
+      for (int bn = 0; bn < 4; ++bn)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const bool hit = lane_row + bm * 32 + 8 * (r >> 2) + (r & 3) == poison_i && lane_col + bn * 32 == poison_j;
+          acc[bm][bn][r] += hit ? 1 : 0;
+        }
+  }
+
+  // red [0,512): column partials by wm, 256 columns each; [512,768): row sums by wn, 128 rows each
+  // One sweep over the registers widens each to int64 once, for both sums (widened twice, in a
+  // sweep per sum, the compiler keeps all 128 widened values and spills).
+  // row sums: per register over the four column blocks, then a butterfly over the 32 lanes of a
+  // half-wave (a 64-bit shuffle is two 32-bit ones), after which every lane holds the sum; lane
+  // l32 keeps that of (bm, r) = (l32 / 16, l32 % 16), so a half-wave's 32 rows are one store per
+  // lane and no branch splits the sweep.
+  // column sums: over this lane's 32 registers of a block column, then across the two half-waves;
+  // both halves then hold all four, and half h stores those of blocks 2h and 2h + 1.
+  long long cs[4] = {0, 0, 0, 0}, mine = 0;
+#pragma unroll
+  for (int bm = 0; bm < 2; ++bm)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      long long rs = 0;
+#pragma unroll
+      for (int bn = 0; bn < 4; ++bn) {
+        const long long v = acc[bm][bn][r];
+        cs[bn] += v;
+        rs += v;
+      }
+#pragma unroll
+      for (int off = 16; off >= 1; off >>= 1) rs += __shfl_xor(rs, off);
+      mine = l32 == bm * 16 + r ? rs : mine;
+    }
+  red[2 * I8_TILE_N + wn * I8_TILE_M + wm * 64 + (l32 >> 4) * 32 + 8 * ((l32 >> 2) & 3) + 4 * half + (l32 & 3)] = mine;
+#pragma unroll
+  for (int bn = 0; bn < 4; ++bn) cs[bn] += __shfl_xor(cs[bn], 32);
+  const long long lo0 = cs[0], lo1 = cs[1], hi0 = cs[2], hi1 = cs[3];  // chosen as values: no indexed array in scratch
+  long long* const cred = red + wm * I8_TILE_N + wn * 128 + 2 * half * 32 + l32;
+  cred[0] = half ? hi0 : lo0;
+  cred[32] = half ? hi1 : lo1;
+  __syncthreads();
+  if (col0 + t < N) colsum[static_cast<size_t>(tm) * N + col0 + t] = red[t] + red[I8_TILE_N + t];
+  const int stripe = 2 * tn + (t >> 7), u = t & 127;  // thread t also owns row u of the stripe of wn = t / 128
+  if (stripe * TILE < N && row0 + u < M) rowsum[static_cast<size_t>(stripe) * M + row0 + u] = red[2 * I8_TILE_N + t];
+
+  if (C != nullptr) {  // --c-out only; the production run never stores M x N
+#pragma unroll
+    for (int bm = 0; bm < 2; ++bm)
+#pragma unroll
+      for (int bn = 0; bn < 4; ++bn)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = lane_row + bm * 32 + 8 * (r >> 2) + (r & 3), col = lane_col + bn * 32;
+          if (row < M && col < N) C[static_cast<size_t>(row) * N + col] = acc[bm][bn][r];
+        }
+  }
+}
+
+// Compiled for gfx950 (-O3, kernel-resource-usage): 204 VGPRs + 0 AGPRs (the 128 accumulator
+// registers are VGPRs), 49152 B LDS, 0 scratch, 0 SGPR/VGPR spills; occupancy 2 waves per SIMD,
+// asked for by the launch bounds: two workgroups per CU, bounded by registers (204 of 256; the
+// LDS, 2 x 48 KB of 160 KB, would admit three).
+//
+// The work split is not that of the other three.  One workgroup (4 waves, 2 x 2) owns a 128x256
+// tile of C and wave w the 64x128 block (w / 2, w % 2) as 2x4 blocks of v_mfma_i32_32x32x32_i8:
+// 8 accumulators of 16 registers, 128 per lane.  Per 32 k a wave reads 2 operands of A and 4 of
+// B (one ds_read_b128 each, 16 int8 per lane) for 8 matrix instructions, 0.75 LDS reads per
+// instruction where the 2x2 layout has 1, and every operand register is used 4 or 2 times.  A
+// 128x256 tile also takes (128 + 256) / (2 * 128 * 256) bytes of global and L2 traffic per
+// product, a third less than 128x128.  The grid is ceil(N / 256) x ceil(M / 128); the checksum
+// stripes stay 128 wide (see the epilogue), so the expectation, verdict and locate kernels and
+// the 128x128 tile index of a mismatch record are shared with the other formats.  An
+// accumulator is written again only after the 7 other instructions of the sweep.
+//
+// Operand layout of the instruction (CDNA4 ISA guide, matrix arithmetic, by analogy with the
+// bf16 instruction; the device agreed: the one-instruction shape of the tests, 32x32x32 on
+// random bytes, is exact against int64, and so are the larger ones): lane l supplies row (A) or column (B) l % 32 and the 16
+// consecutive k values 16 * (l / 32) .. + 15, k ascending from the low byte of register 0;
+// accumulator register r of lane l holds D[8 * (r / 4) + 4 * (l / 32) + r % 4][l % 32].
+//
+// LDS: per stage 128 rows of A and 256 of B, 64 k = 64 bytes each, 24 KB; two stages, 48 KB.
+// The next stage's global loads (6 x 16 bytes per thread: 4 consecutive lanes cover a row, the
+// 256 threads 64 rows, 2 sweeps of A and 4 of B) are in flight during the 16 matrix
+// instructions of this one.  The deeper stage, 128-byte rows (key (r >> 1) & 7, 12 staging
+// registers), halves the barriers but takes 96 KB, one workgroup per CU; the compiler then gives
+// 194 VGPRs + 128 AGPRs at occupancy 1.  Measured alternating at 8192^3, three rounds: 1767.4,
+// 1766.5, 1767.1 TOP/s with 64-byte rows against 1486.9, 1488.8, 1492.3 with 128-byte rows.  A
+// second workgroup to run while one waits at its barrier is worth more than half the barriers,
+// so the 64-byte stage is the one kept.
+//
+// Rows are not padded; the 16-byte chunk c of row r is stored at chunk c ^ key(r),
+//   key(r) = (r >> 2) & 3.
+// With 64 banks of 4 bytes four 64-byte rows fill the banks once, and a 16-byte access at row r,
+// stored chunk p, starts in the 4-bank group 4 * (r & 3) + p of 16.  A ds_read_b128 is served 16
+// lanes at a time, in the sets {0-3, 12-15, 20-23, 24-27}, {4-7, 8-11, 16-19, 28-31} and the
+// same plus 32 (see the FP64 kernel).  A set lies in one half-wave, so all its lanes read one k
+// chunk c, of four groups of four rows; the four rows of a group have the four r & 3 and one
+// key, and the keys of the groups are (r >> 2) & 3 = {0, 3, 1, 2} for the first set and
+// {1, 2, 0, 3} for the second: sixteen distinct 4-bank groups, conflict-free.  The stage
+// writes are 4 lanes per row, so a set covers all four chunks of four rows, rows {0, 3, 5, 6}
+// or {1, 2, 4, 7} of eight, with four distinct r & 3: conflict-free too.
+// SQ_LDS_BANK_CONFLICT over the whole kernel (2048 x 2048 x 1024, counters only): 2048 cycles,
+// 4 per wave over 16 stages of 18 LDS accesses each.  A conflict in the loop would cost at
+// least one cycle per stage, 16 per wave, so the loop has none; the 4 are outside it, where
+// the epilogue stores its 8-byte sums.
+//
+// Rows past M, columns past N and k past K are zero-filled in LDS, never read from memory.
+// K is a multiple of 32 and a row starts 16-byte aligned, so a 16-byte chunk is wholly inside a
+// row or wholly outside it.
+__global__ __launch_bounds__(256, 2) void gemm_abft_i8_kernel(const unsigned char* __restrict__ A,
+                                                              const unsigned char* __restrict__ B, int M, int N, int K,
+                                                              long long* __restrict__ colsum, long long* __restrict__ rowsum,
+                                                              int* __restrict__ C, int poison_i, int poison_j) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * I8_STAGE_BYTES];  // [stage][A, B]
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w >> 1, wn = w & 1;
+  const int l32 = lane & 31, half = lane >> 5;
+  const int row0 = blockIdx.y * I8_TILE_M, col0 = blockIdx.x * I8_TILE_N;
+
+  // global -> LDS copy: rows lr + 64 q, all with the key of lr
+  constexpr int QA = I8_TILE_M / I8_RPS, QB = I8_TILE_N / I8_RPS;
+  const int lr = t / I8_CPR, kc = t % I8_CPR;
+  const int wch = kc ^ i8_key(lr);
+  u32x4 ga[QA], gb[QB];
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+
+#define LOAD_GLOBAL(k0)                                                                        \
+  do {                                                                                         \
+    const int k_ = (k0) + kc * 16;                                                             \
+    _Pragma("unroll") for (int q = 0; q < QA; ++q) {                                           \
+      const int ra_ = row0 + lr + I8_RPS * q;                                                  \
+      ga[q] = (ra_ < M && k_ < K) ? *reinterpret_cast<const u32x4*>(A + static_cast<size_t>(ra_) * K + k_) : zero; \
+    }                                                                                          \
+    _Pragma("unroll") for (int q = 0; q < QB; ++q) {                                           \
+      const int rb_ = col0 + lr + I8_RPS * q;                                                  \
+      gb[q] = (rb_ < N && k_ < K) ? *reinterpret_cast<const u32x4*>(B + static_cast<size_t>(rb_) * K + k_) : zero; \
+    }                                                                                          \
+  } while (0)
+#define STORE_LDS(stage)                                                                       \
+  do {                                                                                         \
+    unsigned char* d_ = lds + (stage) * I8_STAGE_BYTES + lr * I8_KSTEP + wch * 16;             \
+    _Pragma("unroll") for (int q = 0; q < QA; ++q)                                             \
+      *reinterpret_cast<u32x4*>(d_ + I8_RPS * q * I8_KSTEP) = ga[q];                           \
+    _Pragma("unroll") for (int q = 0; q < QB; ++q)                                             \
+      *reinterpret_cast<u32x4*>(d_ + I8_A_BYTES + I8_RPS * q * I8_KSTEP) = gb[q];              \
+  } while (0)
+
+  i32x16 acc[2][4];
+#pragma unroll
+  for (int bm = 0; bm < 2; ++bm)
+#pragma unroll
+    for (int bn = 0; bn < 4; ++bn)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[bm][bn][r] = 0;
+
+  // the lane's chunk of instruction kk is 2 * kk + half, xored with the key of its row (that of
+  // l32, the block rows being multiples of 32): 2 * kk and half share no bit, so it is (2 * kk) ^ xs
+  const int xs = i8_key(l32) ^ half;
+  const int nsteps = (K + I8_KSTEP - 1) / I8_KSTEP;
+  LOAD_GLOBAL(0);
+  STORE_LDS(0);
+  __syncthreads();
+  for (int s = 0; s < nsteps; ++s) {
+    const int stage = s & 1;
+    const bool more = s + 1 < nsteps;
+    if (more) LOAD_GLOBAL((s + 1) * I8_KSTEP);  // in flight while this step multiplies
+    const unsigned char* pa = lds + stage * I8_STAGE_BYTES + (wm * 64 + l32) * I8_KSTEP;
+    const unsigned char* pb = lds + stage * I8_STAGE_BYTES + I8_A_BYTES + (wn * 128 + l32) * I8_KSTEP;
+#pragma unroll
+    for (int kk = 0; kk < I8_KSTEP / 32; ++kk) {
+      const int off = ((2 * kk) ^ xs) * 16;
+      i32x4 a[2], b[4];
+#pragma unroll
+      for (int bl = 0; bl < 2; ++bl) a[bl] = *reinterpret_cast<const i32x4*>(pa + bl * 32 * I8_KSTEP + off);
+#pragma unroll
+      for (int bl = 0; bl < 4; ++bl) b[bl] = *reinterpret_cast<const i32x4*>(pb + bl * 32 * I8_KSTEP + off);
+#pragma unroll
+      for (int bm = 0; bm < 2; ++bm)
+#pragma unroll
+        for (int bn = 0; bn < 4; ++bn)
+          acc[bm][bn] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[bm], b[bn], acc[bm][bn], 0, 0, 0);
+    }
+    // the other stage was last read in step s-1, before the barrier that ended it
+    if (more) STORE_LDS(stage ^ 1);
+    __syncthreads();
+  }
+#undef LOAD_GLOBAL
+#undef STORE_LDS
+
+  abft_epilogue_i8(acc, reinterpret_cast<long long*>(lds), M, N, colsum, rowsum, C, poison_i, poison_j);
+}
+
+// ------------------------------------------------------------------------------------------
 // Expected checksums, in integer arithmetic
 // ------------------------------------------------------------------------------------------
 
@@ -922,6 +1174,48 @@ __global__ __launch_bounds__(256) void expect_f64_kernel(const int* __restrict__
   if (lane == 0) out[static_cast<size_t>(s) * rows_y + y] = sum;
 }
 
+// The INT8 siblings: plain integer multiply-adds.  As stripe_sum_kernel, four k per thread (K is
+// a multiple of 32); a stripe sum is at most 128 * 128 = 2^14.
+__global__ __launch_bounds__(256) void stripe_sum_i8_kernel(const unsigned char* __restrict__ X, int rows, int K,
+                                                            int* __restrict__ e) {
+  const int k = (blockIdx.x * blockDim.x + threadIdx.x) * 4, s = blockIdx.y;
+  if (k >= K) return;
+  const int end = min(rows, (s + 1) * TILE);
+  i32x4 sum = {0, 0, 0, 0};
+  for (int i = s * TILE; i < end; ++i) {
+    const uint32_t v = *reinterpret_cast<const uint32_t*>(X + static_cast<size_t>(i) * K + k);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sum[j] += static_cast<int8_t>(v >> (8 * j));
+  }
+  *reinterpret_cast<i32x4*>(e + static_cast<size_t>(s) * K + k) = sum;
+}
+
+// one wave per (y, s) as in expect_kernel, 16 k per lane per trip; a trip adds 16 products of
+// at most 2^14 * 2^7 in int32, the sum over K is at most 2^37 and is kept in int64
+__global__ __launch_bounds__(256) void expect_i8_kernel(const int* __restrict__ e, int stripes,
+                                                        const unsigned char* __restrict__ Y, int rows_y, int K,
+                                                        long long* __restrict__ out) {
+  const int lane = threadIdx.x & 63, s = blockIdx.y * 4 + (threadIdx.x >> 6), y = blockIdx.x;
+  if (s >= stripes) return;  // whole waves leave; no barrier below
+  const unsigned char* yr = Y + static_cast<size_t>(y) * K;
+  const int* er = e + static_cast<size_t>(s) * K;
+  long long sum = 0;
+  for (int k = lane * 16; k < K; k += 1024) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(yr + k);
+    int part = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const i32x4 eq = *reinterpret_cast<const i32x4*>(er + k + 4 * q);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) part += eq[j] * static_cast<int8_t>(v[q] >> (8 * j));
+    }
+    sum += part;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
+  if (lane == 0) out[static_cast<size_t>(s) * rows_y + y] = sum;
+}
+
 constexpr int MAX_RECORDS = 16;
 
 struct Suspect {  // one checksum that disagrees
@@ -981,6 +1275,28 @@ __global__ __launch_bounds__(256) void verify_f64_kernel(const double* __restric
     if (slot < MAX_RECORDS) {
       const int width = is_col ? N : M;
       Suspect sus = {static_cast<int>(y / width), static_cast<int>(y % width), got - static_cast<double>(want)};
+      (is_col ? res->col : res->row)[slot] = sus;
+    }
+  }
+}
+
+// The INT8 sibling: int64 sums against int64 expectations; only the delta of the report is a double.
+__global__ __launch_bounds__(256) void verify_i64_kernel(const long long* __restrict__ colsum,
+                                                         const long long* __restrict__ colexp, size_t ncol, int N,
+                                                         const long long* __restrict__ rowsum,
+                                                         const long long* __restrict__ rowexp, size_t nrow, int M,
+                                                         GemmResult* res) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t x = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; x < ncol + nrow; x += stride) {
+    const bool is_col = x < ncol;
+    const size_t y = is_col ? x : x - ncol;
+    const long long got = is_col ? colsum[y] : rowsum[y], want = is_col ? colexp[y] : rowexp[y];
+    if (got == want) continue;
+    atomicAdd(&res->count, 1u);
+    const unsigned int slot = atomicAdd(is_col ? &res->ncol : &res->nrow, 1u);
+    if (slot < MAX_RECORDS) {
+      const int width = is_col ? N : M;
+      Suspect sus = {static_cast<int>(y / width), static_cast<int>(y % width), static_cast<double>(got - want)};
       (is_col ? res->col : res->row)[slot] = sus;
     }
   }
@@ -1312,10 +1628,11 @@ static int grid_for(int dev) {
 
 static int usage(const char* why) {
   fprintf(stderr,
-          "%s\nusage: gpu_check gemm [--dtype bf16|mxfp8|mxfp4|fp64] --m M --n N --k K [--seed S] "
+          "%s\nusage: gpu_check gemm [--dtype bf16|mxfp8|mxfp4|fp64|int8] --m M --n N --k K [--seed S] "
           "[--a FILE --b FILE [--sa FILE --sb FILE]] [--c-out FILE] [--poison I,J] "
           "[--device D] [--seconds T]\n         fp64: M and N multiples of 16, K a multiple of 4 and at most 8192; --a/--b "
-          "hold doubles, integers of magnitude <= 65535\n       gpu_check hbm --mib SIZE [--passes P] [--seed S] [--flip WORD:MASK] "
+          "hold doubles, integers of magnitude <= 65535\n         int8: M and N multiples of 32, K a multiple of 32 and at most "
+          "65536; --a/--b hold raw int8 bytes, every value valid\n       gpu_check hbm --mib SIZE [--passes P] [--seed S] [--flip WORD:MASK] "
           "[--device D]\n       gpu_check cu [--k K] [--reps R] [--passes P] [--rounds N] [--seed S] [--flip WG:WORD:MASK] "
           "[--poison WG:WAVE:I,J] [--device D]\n         K a multiple of 16 and at most 304, what 16 waves' operands take of "
           "the 160 KB of LDS; WORD below 40960, WAVE below 16, I,J inside 32x32\n",
@@ -1338,7 +1655,8 @@ static bool read_operand(const std::string& path, size_t elems, std::vector<uint
 }
 
 // exactly `bytes` raw bytes of a microscaling operand; `kind` is MXFP8 (E4M3 bytes of -2 .. 2),
-// MXFP4 (two E2M1 codes of magnitude 0 .. 4 per byte, no negative zero) or 0 (scales: 127, 128)
+// MXFP4 (two E2M1 codes of magnitude 0 .. 4 per byte, no negative zero), 0 (scales: 127, 128) or
+// INT8 (every byte is valid: only the size is checked)
 static bool read_mx(const std::string& path, size_t bytes, int kind, std::vector<unsigned char>* out) {
   FILE* f = fopen(path.c_str(), "rb");
   if (!f) return false;
@@ -1351,6 +1669,7 @@ static bool read_mx(const std::string& path, size_t bytes, int kind, std::vector
   for (unsigned char b : *out) {
     const bool good = kind == MXFP8   ? (b == 0x00 || b == 0x38 || b == 0x40 || b == 0xb8 || b == 0xc0)
                       : kind == MXFP4 ? (fp4(b & 15u) && fp4(b >> 4))
+                      : kind == INT8  ? true
                                       : (b == 127 || b == 128);
     if (!good) return false;
   }
@@ -1375,8 +1694,8 @@ static bool read_f64(const std::string& path, size_t elems, std::vector<uint64_t
 
 struct GemmBuffers {
   unsigned char *A, *B, *SA, *SB;  // the scales only for the microscaling formats
-  float *colsum, *rowsum, *C;      // doubles for FP64
-  int *ea, *eb, *colexp, *rowexp;  // colexp, rowexp: int64 for FP64
+  float *colsum, *rowsum, *C;      // doubles for FP64; int64 sums and an int32 C for INT8
+  int *ea, *eb, *colexp, *rowexp;  // colexp, rowexp: int64 for FP64 and INT8
 };
 
 // One pass: fresh inputs when asked, the GEMM between the two events, the expected checksums.
@@ -1415,6 +1734,22 @@ static void gemm_pass(const GemmBuffers& g, int M, int N, int K, int grid, bool 
     hipLaunchKernelGGL(stripe_sum_f64_kernel, kx_n, b256, 0, 0, B, N, K, g.eb);
     hipLaunchKernelGGL(expect_f64_kernel, ex_col, b256, 0, 0, g.ea, tiles_m, B, N, K, colexp);
     hipLaunchKernelGGL(expect_f64_kernel, ex_row, b256, 0, 0, g.eb, tiles_n, A, M, K, rowexp);
+  } else if constexpr (FMT == INT8) {
+    long long *colexp = reinterpret_cast<long long*>(g.colexp), *rowexp = reinterpret_cast<long long*>(g.rowexp);
+    const dim3 wg_tiles((N + I8_TILE_N - 1) / I8_TILE_N, tiles_m);  // 128 x 256 of C each; the stripes stay 128 wide
+    const dim3 k4_m((K / 4 + 255) / 256, tiles_m), k4_n((K / 4 + 255) / 256, tiles_n);
+    if (generate) {
+      hipLaunchKernelGGL(generate_i8_kernel, dim3(grid), b256, 0, 0, g.A, M, K, mix32(2 * s));
+      hipLaunchKernelGGL(generate_i8_kernel, dim3(grid), b256, 0, 0, g.B, N, K, mix32(2 * s + 1));
+    }
+    CHECK(hipEventRecord(ev0));
+    hipLaunchKernelGGL(gemm_abft_i8_kernel, wg_tiles, b256, 0, 0, g.A, g.B, M, N, K, reinterpret_cast<long long*>(g.colsum),
+                       reinterpret_cast<long long*>(g.rowsum), reinterpret_cast<int*>(g.C), poison_i, poison_j);
+    CHECK(hipEventRecord(ev1));
+    hipLaunchKernelGGL(stripe_sum_i8_kernel, k4_m, b256, 0, 0, g.A, M, K, g.ea);
+    hipLaunchKernelGGL(stripe_sum_i8_kernel, k4_n, b256, 0, 0, g.B, N, K, g.eb);
+    hipLaunchKernelGGL(expect_i8_kernel, ex_col, b256, 0, 0, g.ea, tiles_m, g.B, N, K, colexp);
+    hipLaunchKernelGGL(expect_i8_kernel, ex_row, b256, 0, 0, g.eb, tiles_n, g.A, M, K, rowexp);
   } else {
     if (generate) {
       hipLaunchKernelGGL(generate_mx_kernel<FMT>, dim3(grid), b256, 0, 0, g.A, M, K, mix32(2 * s));
@@ -1445,20 +1780,26 @@ static int run_gemm(int fmt, int M, int N, int K, uint32_t seed, const std::stri
   // 2^32 * K * 128 <= 2^52
   if (fmt == FP64 && (M <= 0 || N <= 0 || K <= 0 || M % 16 || N % 16 || K % 4 || K > 8192))
     return usage("gemm: M and N must be multiples of 16, K a multiple of 4 and at most 8192 (fp64)");
+  // 2^14 * K <= 2^30: every element of C is inside int32
+  if (fmt == INT8 && (M <= 0 || N <= 0 || K <= 0 || M % 32 || N % 32 || K % 32 || K > 65536))
+    return usage("gemm: M and N must be multiples of 32, K a multiple of 32 and at most 65536 (int8)");
   if (a_file.empty() != b_file.empty()) return usage("gemm: --a and --b go together");
   if (!mx ? !(sa_file.empty() && sb_file.empty())
           : (sa_file.empty() != a_file.empty() || sb_file.empty() != a_file.empty()))
     return usage("gemm: --sa and --sb go with --a and --b, for the mx types only");
   if (poison_i >= M || poison_j >= N) return usage("gemm: --poison outside C");
   const size_t a_elems = static_cast<size_t>(M) * K, b_elems = static_cast<size_t>(N) * K;
-  const size_t a_bytes = fmt == FP64 ? a_elems * 8 : fmt == BF16 ? a_elems * 2 : fmt == MXFP8 ? a_elems : a_elems / 2;
-  const size_t b_bytes = fmt == FP64 ? b_elems * 8 : fmt == BF16 ? b_elems * 2 : fmt == MXFP8 ? b_elems : b_elems / 2;
-  const size_t sum_size = fmt == FP64 ? 8 : 4;  // of a checksum, an expectation and an element of C
+  const size_t a_bytes = fmt == FP64 ? a_elems * 8 : fmt == BF16 ? a_elems * 2 : fmt == MXFP4 ? a_elems / 2 : a_elems;
+  const size_t b_bytes = fmt == FP64 ? b_elems * 8 : fmt == BF16 ? b_elems * 2 : fmt == MXFP4 ? b_elems / 2 : b_elems;
+  const size_t sum_size = fmt == FP64 || fmt == INT8 ? 8 : 4;  // of a checksum and an expectation
+  const size_t c_size = fmt == FP64 ? 8 : 4;                    // of an element of C
   std::vector<uint16_t> ha, hb;
   std::vector<uint64_t> da, db;
   if (fmt == FP64 && !a_file.empty() && !(read_f64(a_file, a_elems, &da) && read_f64(b_file, b_elems, &db)))
     return usage("gemm: --a/--b must hold exactly M*K and N*K doubles, integers of magnitude <= 65535");
   std::vector<unsigned char> xa, xb, hsa, hsb;
+  if (fmt == INT8 && !a_file.empty() && !(read_mx(a_file, a_bytes, INT8, &xa) && read_mx(b_file, b_bytes, INT8, &xb)))
+    return usage("gemm: --a/--b must hold exactly M*K and N*K bytes (int8)");
   if (fmt == BF16 && !a_file.empty() && !(read_operand(a_file, a_elems, &ha) && read_operand(b_file, b_elems, &hb)))
     return usage("gemm: --a/--b must hold exactly M*K and N*K bf16 integers in [-2, 2]");
   if (mx && !a_file.empty() &&
@@ -1486,7 +1827,7 @@ static int run_gemm(int fmt, int M, int N, int K, uint32_t seed, const std::stri
   CHECK(hipMalloc(&g.ea, static_cast<size_t>(tiles_m) * K * 4));
   CHECK(hipMalloc(&g.eb, static_cast<size_t>(tiles_n) * K * 4));
   CHECK(hipMalloc(&res, sizeof(GemmResult)));
-  if (!c_out.empty()) CHECK(hipMalloc(&g.C, static_cast<size_t>(M) * N * sum_size));
+  if (!c_out.empty()) CHECK(hipMalloc(&g.C, static_cast<size_t>(M) * N * c_size));
   if (!a_file.empty()) {
     const void* pa = fmt == FP64 ? static_cast<const void*>(da.data()) : fmt == BF16 ? static_cast<const void*>(ha.data()) : xa.data();
     const void* pb = fmt == FP64 ? static_cast<const void*>(db.data()) : fmt == BF16 ? static_cast<const void*>(hb.data()) : xb.data();
@@ -1512,8 +1853,13 @@ static int run_gemm(int fmt, int M, int N, int K, uint32_t seed, const std::stri
     if (fmt == BF16) gemm_pass<BF16>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
     else if (fmt == MXFP8) gemm_pass<MXFP8>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
     else if (fmt == MXFP4) gemm_pass<MXFP4>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
-    else gemm_pass<FP64>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
-    if (fmt == FP64)
+    else if (fmt == FP64) gemm_pass<FP64>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
+    else gemm_pass<INT8>(g, M, N, K, grid, a_file.empty(), s, poison_i, poison_j, ev0, ev1);
+    if (fmt == INT8)
+      hipLaunchKernelGGL(verify_i64_kernel, dim3(grid), dim3(256), 0, 0, reinterpret_cast<const long long*>(g.colsum),
+                         reinterpret_cast<const long long*>(g.colexp), ncol, N, reinterpret_cast<const long long*>(g.rowsum),
+                         reinterpret_cast<const long long*>(g.rowexp), nrow, M, res);
+    else if (fmt == FP64)
       hipLaunchKernelGGL(verify_f64_kernel, dim3(grid), dim3(256), 0, 0, reinterpret_cast<const double*>(g.colsum),
                          reinterpret_cast<const long long*>(g.colexp), ncol, N, reinterpret_cast<const double*>(g.rowsum),
                          reinterpret_cast<const long long*>(g.rowexp), nrow, M, res);
@@ -1530,7 +1876,7 @@ static int run_gemm(int fmt, int M, int N, int K, uint32_t seed, const std::stri
   } while (host.count == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < seconds);
 
   if (C != nullptr) {
-    std::vector<unsigned char> hc(static_cast<size_t>(M) * N * sum_size);  // floats, or doubles for fp64
+    std::vector<unsigned char> hc(static_cast<size_t>(M) * N * c_size);  // floats, doubles for fp64, int32 for int8
     CHECK(hipMemcpy(hc.data(), C, hc.size(), hipMemcpyDeviceToHost));
     FILE* f = fopen(c_out.c_str(), "wb");
     if (!f || fwrite(hc.data(), 1, hc.size(), f) != hc.size()) return usage("gemm: cannot write --c-out");
@@ -1552,7 +1898,7 @@ static int run_gemm(int fmt, int M, int N, int K, uint32_t seed, const std::stri
   const double tflops = gemm_ms > 0 ? 2.0 * M * N * K * passes / (gemm_ms * 1e-3) / 1e12 : 0.0;
   printf("{\"check\":\"gemm\",%s\"ok\":%s,\"m\":%d,\"n\":%d,\"k\":%d,\"passes\":%d,\"mismatch_count\":%u,\"mismatches\":[%s],"
          "\"tflops\":%.3f}\n",
-         fmt == MXFP8 ? "\"dtype\":\"mxfp8\"," : fmt == MXFP4 ? "\"dtype\":\"mxfp4\"," : fmt == FP64 ? "\"dtype\":\"fp64\"," : "",
+         fmt == MXFP8 ? "\"dtype\":\"mxfp8\"," : fmt == MXFP4 ? "\"dtype\":\"mxfp4\"," : fmt == FP64 ? "\"dtype\":\"fp64\"," : fmt == INT8 ? "\"dtype\":\"int8\"," : "",
          ok ? "true" : "false", M, N, K,
          passes, host.count, recs.c_str(), tflops);
   return ok ? 0 : 1;
@@ -1770,8 +2116,9 @@ int main(int argc, char** argv) {
     else if (gemm && k == "--sb") sb_file = v;
     else if (gemm && k == "--dtype") {
       const std::string d = v;
-      if (d != "bf16" && d != "mxfp8" && d != "mxfp4" && d != "fp64") return usage("--dtype wants bf16, mxfp8, mxfp4 or fp64");
-      fmt = d == "bf16" ? BF16 : d == "mxfp8" ? MXFP8 : d == "mxfp4" ? MXFP4 : FP64;
+      if (d != "bf16" && d != "mxfp8" && d != "mxfp4" && d != "fp64" && d != "int8")
+        return usage("--dtype wants bf16, mxfp8, mxfp4, fp64 or int8");
+      fmt = d == "bf16" ? BF16 : d == "mxfp8" ? MXFP8 : d == "mxfp4" ? MXFP4 : d == "fp64" ? FP64 : INT8;
     }
     else if (gemm && k == "--c-out") c_out = v;
     else if (gemm && k == "--seconds") seconds = atof(v);
@@ -1799,7 +2146,7 @@ int main(int argc, char** argv) {
                       flip_mask, poison_wg, poison_wave,           poison_i, poison_j};  // the default K is the cap
     return run_cu(a, rounds, device);
   }
-  if (K == 0) K =fmt == BF16 || fmt == FP64 ? 4096 : fmt == MXFP8 ? 8192 : 2048;  // the default: for the mx types the format's cap
+  if (K == 0) K = fmt == BF16 || fmt == FP64 ? 4096 : fmt == MXFP8 || fmt == INT8 ? 8192 : 2048;  // the default: for the mx types the format's cap
   if (mode == "gemm")
     return run_gemm(fmt, M, N, K, seed, a_file, b_file, sa_file, sb_file, c_out, poison_i, poison_j, device, seconds);
   return run_hbm(mib, passes, seed, flip, flip_word, flip_mask, device);

@@ -81,8 +81,8 @@ def main(argv=None) -> int:
         ap.add_argument("--device", type=int, default=0)
         ap.add_argument("--quick", action="store_true", help="1024^3 GEMM, one pass, 256 MiB of HBM")
         ap.add_argument("--json", action="store_true", help="print the whole record")
-        ap.add_argument("--dtypes", default="bf16", help="GEMM formats, comma-separated: bf16[,mxfp8][,mxfp4][,fp64]")
-        ap.add_argument("--all-formats", action="store_true", help="the same as --dtypes bf16,mxfp8,mxfp4; for FP64 name it: --dtypes bf16,fp64")
+        ap.add_argument("--dtypes", default="bf16", help="GEMM formats, comma-separated: bf16[,mxfp8][,mxfp4][,fp64][,int8]")
+        ap.add_argument("--all-formats", action="store_true", help="the same as --dtypes bf16,mxfp8,mxfp4; for FP64 or INT8 name it: --dtypes bf16,fp64,int8")
         ap.add_argument("--per-cu", action="store_true", help="also check every CU's LDS and matrix units, named by XCC, SE and CU")
         a = ap.parse_args(argv)
         quick = {"gemm": (1024, 1024, 1024), "seconds": 0.0, "hbm_mib": 256.0} if a.quick else {}

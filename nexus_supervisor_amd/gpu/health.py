@@ -7,6 +7,9 @@ exact: pass and fail need no tolerance.  On request the same GEMM check also run
 microscaling formats (MXFP8, MXFP4) on the scaled matrix path, which the bf16 one never touches,
 and in FP64 on the double-precision matrix path (``v_mfma_f64_16x16x4_f64``), where a 53-bit
 significand leaves room for wide data: random 17-bit signed integers, not five small values.
+``"int8"`` runs it on the integer matrix path (``v_mfma_i32_32x32x32_i8``) with bytes uniform over
+all 256 values: int8 products accumulated in int32 are exact for any data, so this is the one fast
+check whose operands toggle every bit.
 Also on request, ``gpu_check cu`` says where on the die: one workgroup per compute unit sweeps that
 CU's whole 160 KB of LDS and runs a known-answer matrix chain on each of its SIMDs, and a fault is
 named by XCC, shader engine and CU, which in CPX mode is one partition and not the whole OAM.
@@ -55,7 +58,7 @@ def _run_step(cmd: List[str], timeout: float) -> Tuple[Dict[str, Any], Optional[
 # (``run_gemm`` in csrc/health/gpu_check.hip enforces the same)
 MX_K_CAP = {"mxfp8": 8192, "mxfp4": 2048}
 # the same for every format that adds a child to the bf16 one
-EXTRA_K_CAP = {**MX_K_CAP, "fp64": 8192}
+EXTRA_K_CAP = {**MX_K_CAP, "fp64": 8192, "int8": 65536}
 
 
 def check_gpu(device: int = 0, *, gemm: Sequence[int] = (8192, 8192, 4096), seconds: float = 2.0,
@@ -64,9 +67,10 @@ def check_gpu(device: int = 0, *, gemm: Sequence[int] = (8192, 8192, 4096), seco
     """Run the GEMM check, then the HBM check, on ``device``.  ``hbm_mib=None`` lets the
     binary size the sweep (the smaller of 32 GiB and half of what is free); ``binary``
     overrides the built ``bin/gpu_check``.  ``dtypes`` names the GEMM formats: ``"bf16"``
-    always, and each of ``"mxfp8"``, ``"mxfp4"``, ``"fp64"`` adds one child after it (the FP64
-    one after the microscaling ones) with the same M and N and K capped at ``EXTRA_K_CAP``,
-    its record under ``"gemm_mxfp8"`` / ``"gemm_mxfp4"`` / ``"gemm_fp64"``.  ``cu=True`` adds the
+    always, and each of ``"mxfp8"``, ``"mxfp4"``, ``"fp64"``, ``"int8"`` adds one child after it (the
+    FP64 one after the microscaling ones, the INT8 one last) with the same M and N and K capped at
+    ``EXTRA_K_CAP``, its record under ``"gemm_mxfp8"`` / ``"gemm_mxfp4"`` / ``"gemm_fp64"`` /
+    ``"gemm_int8"``.  ``cu=True`` adds the
     per-CU check (``gpu_check cu``: each compute unit's whole LDS and the matrix unit of each of
     its SIMDs, named by XCC, SE and CU) after the GEMM children, its record under ``"cu"``.  Returns
     ``{"ok", "device", "gemm", "hbm", "elapsed_s", "error"}`` and those: ``ok`` only if every
@@ -74,7 +78,7 @@ def check_gpu(device: int = 0, *, gemm: Sequence[int] = (8192, 8192, 4096), seco
     that ended by signal or timeout nothing more is started: the rest is ``{"skipped": True}``."""
     if "bf16" not in dtypes or any(d != "bf16" and d not in EXTRA_K_CAP for d in dtypes) or len(set(dtypes)) != len(dtypes):
         raise ValueError(f"dtypes must be 'bf16' and any of {sorted(EXTRA_K_CAP)}, each once: {tuple(dtypes)!r}")
-    extra = [d for d in dtypes if d in MX_K_CAP] + [d for d in dtypes if d == "fp64"]  # fp64 after the mx ones
+    extra = [d for d in dtypes if d in MX_K_CAP] + [d for d in ("fp64", "int8") if d in dtypes]  # fp64 after the mx ones, then int8
     if binary is None:
         from .. import _build
 
