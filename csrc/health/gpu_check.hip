@@ -65,6 +65,39 @@
 //        otherwise idle device.  --flip xors one LDS word of workgroup WG after the first write
 //        pass, --poison adds 1 to element I,J of one wave's block after its first chain, both in
 //        round 0 only.
+//   gpu_check attn [--heads H] [--seq S] [--d 64|128] [--causal] [--seed S] [--seconds T]
+//                  [--q FILE --k FILE --v FILE] [--o-out FILE] [--ml-out FILE]
+//                  [--poison H,I,C] [--device D]
+//        fused attention, the data flow none of the above has: matrix accumulators read back by
+//        the vector ALU and fed to the matrix unit again as operands, register to register; row
+//        reductions across lanes; the transcendental unit (v_exp_f32); the fp32 -> bf16 pack;
+//        the per-row rescale of live accumulators (online softmax); with --causal the masked
+//        diagonal tile.  Per head, with Q, K, V of shape S x d in bf16, row-major:
+//          s[i][j] = sum_c Q[i][c] K[j][c]     (no 1/sqrt(d): it would add nothing to the check)
+//          m[i] = max_j s[i][j],  p[i][j] = 2^(s[i][j] - m[i]),  l[i] = sum_j p[i][j]
+//          O'[i][c] = sum_j p[i][j] V[j][c]    (unnormalised; with --causal j runs over j <= i)
+//        The final division by l is not correctly rounded on the device, so it stays out:
+//        v_rcp_f32 remains uncovered.  Both sides are exact and the comparison is ==:
+//          K and V elements are integers in [-2, 2] (the five values of the GEMM inputs) and every
+//          row of Q holds integers with sum_c |Q[i][c]| <= 3, so |s| <= 6 and s - m is an integer
+//          in [-12, 0]: every p is a power of two no smaller than 2^-12, exact in bf16.
+//          With online softmax the running maximum never exceeds the final one, so at every step
+//          l and O' are integer multiples of 2^-12 with l <= S and |O'| <= 2 S; fp32 holds all of
+//          them exactly, in any summation order, while 2 S 2^12 <= 2^24, that is S <= 2048.
+//          The rescale factor 2^(m_old - m_new) is a power of two no smaller than 2^-12 and
+//          keeps the unit; the fp32 -> bf16 conversion of a power of two is exact under any
+//          rounding mode.
+//        S is a multiple of 64 and at most 2048, d is 64 or 128, H from 1 to 65535 (the grid);
+//        the defaults are 64 heads, S 2048, d 128, not causal, a pass of about a millisecond.
+//        --q/--k/--v hold H*S*d bf16 each and every element is checked against the rules above
+//        before the device is opened.  When generated, a row of Q has +-1 at three hashed
+//        columns, summed where they collide.  The expected O', l and m come once per run from an
+//        integer kernel (shifts, no floating-point instruction); the device's fp32 results are
+//        decoded to units of 2^-12 by bit pattern and compared after every pass.  --o-out and
+//        --ml-out dump O' (H x S x d fp32) and the pairs (m, l) (H x S x 2 fp32); --poison adds
+//        2^-12 to O'[H][I][C].  A mismatch record is {"kind": "o" | "l" | "m", "head", "i", "c",
+//        "delta"}: delta in units of 2^-12, c 0 for l and m; wrong O' elements first, then l and
+//        m, each in index order.
 //
 // The last stdout line is one JSON object.  Exit 0: every check passed; 1: wrong data found;
 // 2: usage error; 3: a HIP call failed.  --poison and --flip are the detectors' self-tests:
@@ -1617,6 +1650,399 @@ __global__ __launch_bounds__(CU_THREADS) void cu_check_kernel(CuResult* __restri
 }
 
 // ------------------------------------------------------------------------------------------
+// Fused attention: S^T = K Q^T, base-2 online softmax, O'^T = V^T P^T
+// ------------------------------------------------------------------------------------------
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int AT_QROWS = 128;                // query rows per workgroup, 32 per wave
+constexpr int AT_KEYS = 64;                  // keys per LDS stage
+constexpr int AT_VPITCH = AT_KEYS * 2 + 16;  // a row of the transposed V tile: 64 keys and a pad
+constexpr int AT_FRAC = 12;                  // every result is a multiple of 2^-12
+constexpr int AT_S_CAP = 2048;               // 2 S 2^12 <= 2^24
+constexpr float AT_M0 = -64.0f;              // where the running maximum starts: below every score (|s| <= 6)
+
+// The Q inputs: row `row` holds +-1 at three hashed columns, summed where they collide, so the
+// sum of magnitudes of a row is at most 3 by construction.  One thread writes 8 consecutive bf16.
+__global__ __launch_bounds__(256) void generate_q_kernel(uint16_t* __restrict__ x, size_t rows, int D, uint32_t seed) {
+  const size_t chunks = rows * (D / 8);
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t c = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; c < chunks; c += stride) {
+    const uint32_t row = static_cast<uint32_t>(c / (D / 8)), col = static_cast<uint32_t>(c % (D / 8)) * 8;
+    const uint32_t hr = mix32(seed ^ (row * 0x9e3779b9u));
+    int v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t k = 0; k < 3; ++k) {
+      const uint32_t h = mix32(hr + k);
+      const uint32_t at = (h >> 1) % static_cast<uint32_t>(D) - col;  // wraps to a large value when outside the chunk
+#pragma unroll
+      for (uint32_t e = 0; e < 8; ++e) v[e] += at == e ? ((h & 1u) ? -1 : 1) : 0;
+    }
+    u32x4 out;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int mag = v[e] < 0 ? -v[e] : v[e];  // 0, 1, 2, 3 -> 0, 1.0, 2.0, 1.5 * 2
+      const uint32_t bits = (v[e] < 0 ? 0x8000u : 0u) | (mag == 0 ? 0u : mag == 1 ? 0x3f80u : mag == 2 ? 0x4000u : 0x4040u);
+      if (e & 1) out[e / 2] |= bits << 16;
+      else out[e / 2] = bits;
+    }
+    *reinterpret_cast<u32x4*>(x + c * 8) = out;
+  }
+}
+
+// The softmax of one 64-key tile for this lane's query, on the 32 scores the lane holds, and the
+// exchange with lane l ^ 32 that holds the other 32.  Updates the running maximum and sum and
+// packs the probabilities as the four B operands of the O' step; returns the rescale factor.  MASK: entries with key > query
+// get p = 0 and stay out of the maximum.
+template <bool MASK>
+__device__ __forceinline__ float attn_softmax(const f32x16 (&sc)[2], int lane_key, int qi, float& m_run, float& l_run,
+                                             bf16x8 (&pf)[4]) {
+  float m_new = m_run;
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const bool on = !MASK || lane_key + 32 * kb + 8 * (r >> 2) + (r & 3) <= qi;
+      m_new = on ? fmaxf(m_new, sc[kb][r]) : m_new;
+    }
+  m_new = fmaxf(m_new, __shfl_xor(m_new, 32));
+  float psum = 0.0f;
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const bool on = !MASK || lane_key + 32 * kb + 8 * (r >> 2) + (r & 3) <= qi;
+      const float p = on ? __builtin_amdgcn_exp2f(sc[kb][r] - m_new) : 0.0f;
+      psum += p;
+      pf[2 * kb + (r >> 3)][r & 7] = static_cast<__bf16>(p);
+    }
+  psum += __shfl_xor(psum, 32);
+  const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);  // the rescale factor, for O' as well
+  l_run = l_run * alpha + psum;
+  m_run = m_new;
+  return alpha;
+}
+
+// Compiled for gfx950 (-O3, kernel-resource-usage):
+//   d = 64:  129 VGPRs (causal 142) + 0 AGPRs, 36864 B LDS, 0 scratch, 0 SGPR/VGPR spills, occupancy 3
+//   d = 128: 201 VGPRs (causal 208) + 0 AGPRs, 71680 B LDS, 0 scratch, 0 SGPR/VGPR spills, occupancy 2
+// waves per SIMD.  The launch bounds ask for two workgroups per CU: left alone the compiler puts
+// the O' accumulators into AGPRs (190 + 64, causal 199 + 64 at occupancy 1) and moves all 64 to
+// VGPRs and back for every rescale.  At d = 128 a lane holds 64 registers of O', 32 of Q, 32 of
+// scores, 16 of packed P and 32 of global loads in flight.
+//
+// One forward pass of flash attention per (query block, head): O'[i][c] = sum_j 2^(s[i][j] - m[i]) V[j][c]
+// with s = Q K^T, m the row maximum and l the row sum of the powers; base 2, no 1/sqrt(d), no
+// final division (see the header).  Its design is not that of the GEMMs.
+//
+// Work split.  The grid is (ceil(S / 128), H).  A workgroup has 4 waves and wave w owns the 32
+// query rows from 128 * block + 32 w for the whole kernel; S is a multiple of 64, so the last
+// block may have rows for two waves only, and the other two just help to copy and keep the
+// barriers.  Tiles of 64 keys of K and V move through LDS, double buffered: the global loads of
+// tile kt + 1 are in flight while tile kt is computed, and are stored after it.
+//
+// Transposed formulation.  The wave computes S^T = K Q^T with v_mfma_f32_32x32x16_bf16 (layout
+// as in gemm_abft_kernel's comment): K rows are the A operand from LDS, the wave's 32 rows of Q
+// the B operand, lane l holding Q[q0 + l % 32][16 t + 8 (l / 32) .. + 7] in d / 16 x 4 registers
+// for the whole kernel.  Register r of the accumulator of key block kb (32 keys) then holds, in
+// lane l, the score of ONE query, l % 32, for key 32 kb + 8 (r / 4) + 4 (l / 32) + r % 4: a lane
+// has 32 scores of its query per tile, the lane l ^ 32 the other 32.  Row maximum and row sum are
+// an in-lane reduction over those registers and one exchange with lane l ^ 32; m, l and the
+// rescale factor 2^(m_old - m_new) are per lane, and rescaling O' is a multiply of the lane's own
+// accumulators: O'^T = V^T P^T has the query in the column, l % 32, too.  Nothing is broadcast.
+//
+// P never leaves registers.  p = 2^(s - m) comes from v_exp_f32 (__builtin_amdgcn_exp2f), eight
+// of them are packed to bf16 (v_cvt_pk_bf16_f32) and are the B operand of step u of O'^T: the
+// registers 8 (u % 2) .. + 7 of key block u / 2.  As an operand they stand for k = 8 (l / 32) .. + 7,
+// but hold the keys {16 u + 4 h + 0..3, 16 u + 8 + 4 h + 0..3}, h = l / 32.  A sum over k does
+// not care which key sits at which k as long as both operands agree, so the A operand, V^T, is
+// read for the same keys in the same order and nothing is shuffled between lanes.
+//
+// V reaches the matrix unit key-contiguous by being written transposed into LDS when the stage
+// is stored: row c of the stage holds the 64 keys of column c, and key k of a 16-key group sits
+// at position k with bits 2 and 3 swapped, so the eight keys a lane needs are 16 consecutive
+// bytes, one ds_read_b128.  (Chosen over the transposing LDS loads of gfx950, ds_read_b64_tr_b16:
+// their lane-to-element map would have been one more supposition to settle on the device, on the
+// side of the comparison that has to be trusted; a transposed store is plain address arithmetic.
+// It costs 8 ds_write_b32 per 2 keys x 8 columns where a straight copy has 2 ds_write_b128.)
+// A thread takes two adjacent keys and 8 columns from global memory, pairs the two keys' values
+// of a column in one word and writes 8 words, one per column row.
+//
+// LDS: per stage 64 rows of K, d bf16 + 16 B pad (144 or 272 B), and d rows of V^T, 64 keys +
+// 16 B pad (144 B); two stages, 36 KB (d = 64) or 70 KB (d = 128).  Rows are padded, as in the
+// bf16 GEMM.  The operand reads are one ds_read_b128 per lane, served 16 lanes at a time, either
+// 16 consecutive lanes or the sets {0-3, 12-15, 20-23, 24-27}, {4-7, 8-11, 16-19, 28-31} (+ 32)
+// of the FP64 kernel's comment: each set reads 16 rows with 16 distinct r mod 16 at one offset.
+// With 64 banks of 4 bytes row r starts at bank 36 r mod 64 = 4 (9 r mod 16) (pitch 144) or
+// 68 r mod 64 = 4 (r mod 16) (pitch 272): sixteen distinct 4-bank groups, conflict-free.  The
+// K stage writes are whole 16-byte chunks, 8 or 16 lanes per row, as in the bf16 GEMM.  The V^T
+// writes are ds_write_b32, 64 lanes at once: lane l of a wave writes key pair l % 32 (word
+// position: a bijection of it) of column rows 8 cc + e, cc = 2 w + l / 32; the word address is
+// 36 (8 cc + e) + position = 32 cc + 36 e + position mod 64, and two values of cc 32 apart with 32
+// positions each cover every bank once: conflict-free.
+//
+// Causal.  Key tiles wholly above the diagonal of the query block are not visited (the block
+// stops after tile 2 * block + 1), and a wave skips a tile that is wholly above its own 32 rows.
+// In a tile that the diagonal crosses, an entry with key > query gets p = 0 and its score is
+// kept out of the running maximum.  Tile 0 holds key 0, which no row masks, so after tile 0
+// every row has a true maximum.
+//
+// The running maximum starts at -64, below every score, so the first tile is no special case:
+// its m_new is the tile's own maximum, at least -6, the rescale factor is 2^(-64 - m_new), a
+// normal fp32 between 2^-70 and 2^-58, and l and O' are +0: 0 x a finite factor is exactly 0.
+//
+// Every key tile lies inside S (a multiple of 64), and Q rows and the stores are guarded by the
+// wave's `live`, so no address outside the three inputs and two outputs is formed.
+template <int D, bool CAUSAL>
+__global__ __launch_bounds__(256, 2) void attn_kernel(const uint16_t* __restrict__ Q, const uint16_t* __restrict__ K,
+                                                   const uint16_t* __restrict__ V, int S, float* __restrict__ O,
+                                                   float* __restrict__ ML, int poison_h, int poison_i, int poison_c) {
+  constexpr int KP = 2 * D + 16;                                  // pitch of a K row in LDS
+  constexpr int K_BYTES = AT_KEYS * KP, STAGE = K_BYTES + D * AT_VPITCH;
+  constexpr int CPR = D / 8, RPS = 256 / CPR, KQ = AT_KEYS / RPS;  // K copy: chunks per row, rows per sweep, sweeps
+  constexpr int VI = D / 64;                                       // V copy: (key pair, 8 columns) items per thread
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * STAGE];  // [stage][K, V^T]
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, l32 = lane & 31, half = lane >> 5;
+  // causal blocks differ in length, 2 to S / 64 tiles: the long ones are dispatched first
+  const int qb = CAUSAL ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+  const int head = blockIdx.y, q0 = qb * AT_QROWS + w * 32, qi = q0 + l32;  // the wave's first query, the lane's
+  const size_t hbase = static_cast<size_t>(head) * S;  // rows before this head
+  const bool live = q0 < S;
+  const int ntiles = CAUSAL ? min(S / AT_KEYS, 2 * qb + 2) : S / AT_KEYS;
+
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+  bf16x8 qf[D / 16];
+#pragma unroll
+  for (int tt = 0; tt < D / 16; ++tt)
+    qf[tt] = __builtin_bit_cast(bf16x8, live ? *reinterpret_cast<const u32x4*>(Q + (hbase + qi) * D + tt * 16 + half * 8) : zero);
+
+  const int lr = t / CPR, kc = t % CPR;
+  u32x4 gk[KQ], gv[VI][2];
+#define LOAD_GLOBAL(tile)                                                                      \
+  do {                                                                                         \
+    const size_t r0_ = hbase + static_cast<size_t>(tile) * AT_KEYS;                            \
+    _Pragma("unroll") for (int q = 0; q < KQ; ++q)                                             \
+      gk[q] = *reinterpret_cast<const u32x4*>(K + (r0_ + lr + RPS * q) * D + kc * 8);          \
+    _Pragma("unroll") for (int i = 0; i < VI; ++i) {                                           \
+      const int x_ = t + 256 * i, pr_ = x_ & 31, cc_ = x_ >> 5;                                \
+      gv[i][0] = *reinterpret_cast<const u32x4*>(V + (r0_ + 2 * pr_) * D + cc_ * 8);           \
+      gv[i][1] = *reinterpret_cast<const u32x4*>(V + (r0_ + 2 * pr_ + 1) * D + cc_ * 8);       \
+    }                                                                                          \
+  } while (0)
+#define STORE_LDS(stage)                                                                       \
+  do {                                                                                         \
+    unsigned char* sk_ = lds + (stage) * STAGE + lr * KP + kc * 16;                            \
+    _Pragma("unroll") for (int q = 0; q < KQ; ++q) *reinterpret_cast<u32x4*>(sk_ + RPS * q * KP) = gk[q]; \
+    _Pragma("unroll") for (int i = 0; i < VI; ++i) {                                           \
+      const int x_ = t + 256 * i, key_ = 2 * (x_ & 31), cc_ = x_ >> 5;                         \
+      const int pos_ = (key_ & ~12) | ((key_ & 4) << 1) | ((key_ & 8) >> 1);                   \
+      unsigned char* sv_ = lds + (stage) * STAGE + K_BYTES + cc_ * 8 * AT_VPITCH + pos_ * 2;   \
+      _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                          \
+        const uint32_t a_ = gv[i][0][j], b_ = gv[i][1][j];                                     \
+        *reinterpret_cast<uint32_t*>(sv_ + (2 * j) * AT_VPITCH) = (a_ & 0xffffu) | (b_ << 16); \
+        *reinterpret_cast<uint32_t*>(sv_ + (2 * j + 1) * AT_VPITCH) = (a_ >> 16) | (b_ & 0xffff0000u); \
+      }                                                                                        \
+    }                                                                                          \
+  } while (0)
+
+  f32x16 acc[D / 32];  // O'^T: block cb holds columns 32 cb .. + 31 of the wave's 32 queries
+#pragma unroll
+  for (int cb = 0; cb < D / 32; ++cb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[cb][r] = 0.0f;
+  float m_run = AT_M0, l_run = 0.0f;
+
+  LOAD_GLOBAL(0);
+  STORE_LDS(0);
+  __syncthreads();
+  for (int kt = 0; kt < ntiles; ++kt) {
+    const int stage = kt & 1, key0 = kt * AT_KEYS;
+    const bool more = kt + 1 < ntiles;
+    if (more) LOAD_GLOBAL(kt + 1);  // in flight while this tile is computed
+    if (live && !(CAUSAL && key0 > q0 + 31)) {
+      const unsigned char* sk = lds + stage * STAGE + l32 * KP + half * 16;
+      f32x16 sc[2];
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sc[kb][r] = 0.0f;
+#pragma unroll
+        for (int tt = 0; tt < D / 16; ++tt)
+          sc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(sk + kb * 32 * KP + tt * 32),
+                                                           qf[tt], sc[kb], 0, 0, 0);
+      }
+      // the diagonal crosses this tile for some row of the wave: only then is an entry compared with its row
+      const bool diag = CAUSAL && key0 + AT_KEYS - 1 > q0;
+      const int lane_key = key0 + 4 * half;  // entry (kb, r) is key lane_key + 32 kb + 8 (r / 4) + r % 4
+      bf16x8 pf[4];
+      const float alpha = diag ? attn_softmax<true>(sc, lane_key, qi, m_run, l_run, pf)
+                               : attn_softmax<false>(sc, lane_key, qi, m_run, l_run, pf);
+#pragma unroll
+      for (int cb = 0; cb < D / 32; ++cb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[cb][r] *= alpha;
+      const unsigned char* sv = lds + stage * STAGE + K_BYTES + l32 * AT_VPITCH + half * 16;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int cb = 0; cb < D / 32; ++cb)
+          acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(sv + cb * 32 * AT_VPITCH + u * 32),
+                                                           pf[u], acc[cb], 0, 0, 0);
+    }
+    // the other stage was last read in tile kt-1, before the barrier that ended it
+    if (more) STORE_LDS(stage ^ 1);
+    __syncthreads();
+  }
+#undef LOAD_GLOBAL
+#undef STORE_LDS
+
+  if (!live) return;  // past the last barrier
+  // register r of block cb is O'[qi][32 cb + 8 (r / 4) + 4 half + r % 4]: four consecutive columns per r / 4
+  if (poison_h == head && poison_i == qi) {  // detector self-test: one element off by one unit
+#pragma unroll
+    for (int cb = 0; cb < D / 32; ++cb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[cb][r] += 32 * cb + 8 * (r >> 2) + 4 * half + (r & 3) == poison_c ? 0x1p-12f : 0.0f;
+  }
+  float* const orow = O + (hbase + qi) * D + 4 * half;
+#pragma unroll
+  for (int cb = 0; cb < D / 32; ++cb)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const f32x4 v = {acc[cb][4 * g], acc[cb][4 * g + 1], acc[cb][4 * g + 2], acc[cb][4 * g + 3]};
+      *reinterpret_cast<f32x4*>(orow + 32 * cb + 8 * g) = v;
+    }
+  if (half == 0) {
+    const f32x2 ml = {m_run, l_run};
+    *reinterpret_cast<f32x2*>(ML + (hbase + qi) * 2) = ml;
+  }
+}
+
+// The expected side, in integers: nothing below is shared with attn_kernel and no floating-point
+// instruction is on it.  A Q element is an integer of magnitude < 256 in bf16 (here at most 3),
+// decoded by shifts; false for a fraction, an infinity, a NaN.
+__host__ __device__ static inline bool bf16_whole(uint32_t bits16, int* out) {
+  const int e = (bits16 >> 7) & 0xff, frac = bits16 & 0x7f;
+  *out = 0;
+  if (e == 0) return frac == 0;          // +-0; a subnormal is a fraction
+  if (e < 127 || e > 134) return false;  // below 1; 256 and above, infinity, NaN
+  const int sig = 0x80 | frac, drop = 134 - e;  // the value is sig * 2^(e - 134)
+  if (sig & ((1 << drop) - 1)) return false;
+  *out = (bits16 & 0x8000u) ? -(sig >> drop) : sig >> drop;
+  return true;
+}
+
+// One workgroup per (row i, head), in units of 2^-12: ofix[i][c] = sum_j V[j][c] << (s_j - m + 12),
+// mlfix[i] = {m << 12, sum_j 1 << (s_j - m + 12)}, over j <= i when causal.  Two passes over the
+// keys: the scores and their maximum, then the sums.  s_j - m + 12 is in [0, 12], |ofix| <= 2 S 2^12.
+__global__ __launch_bounds__(256) void expect_attn_kernel(const uint16_t* __restrict__ Q, const uint16_t* __restrict__ K,
+                                                          const uint16_t* __restrict__ V, int S, int D, int causal,
+                                                          int* __restrict__ ofix, int* __restrict__ mlfix) {
+  __shared__ int qrow[128], score[AT_S_CAP], red[256];
+  const int t = threadIdx.x, i = blockIdx.x;
+  const size_t hbase = static_cast<size_t>(blockIdx.y) * S;
+  const int n = causal ? i + 1 : S;
+  if (t < D) bf16_whole(Q[(hbase + i) * D + t], &qrow[t]);
+  __syncthreads();
+  int mx = INT32_MIN;
+  for (int j = t; j < n; j += 256) {
+    const uint16_t* kr = K + (hbase + j) * D;
+    int s = 0;
+    for (int c = 0; c < D; c += 8) {
+      const u32x4 v = *reinterpret_cast<const u32x4*>(kr + c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        s += qrow[c + 2 * e] * bf16_small_int(v[e] & 0xffffu) + qrow[c + 2 * e + 1] * bf16_small_int(v[e] >> 16);
+    }
+    score[j] = s;
+    mx = max(mx, s);
+  }
+  red[t] = mx;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if (t < off) red[t] = max(red[t], red[t + off]);
+    __syncthreads();
+  }
+  const int m = red[0];
+  __syncthreads();
+  int lsum = 0;
+  for (int j = t; j < n; j += 256) lsum += 1 << (score[j] - m + AT_FRAC);
+  red[t] = lsum;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if (t < off) red[t] += red[t + off];
+    __syncthreads();
+  }
+  if (t == 0) {
+    mlfix[(hbase + i) * 2] = m * (1 << AT_FRAC);
+    mlfix[(hbase + i) * 2 + 1] = red[0];
+  }
+  __syncthreads();
+  // thread t adds column t % D over the keys of slice t / D, then the 256 / D slices are added
+  const int c = t % D, slices = 256 / D;
+  int o = 0;
+  for (int j = t / D; j < n; j += slices) o += bf16_small_int(V[(hbase + j) * D + c]) * (1 << (score[j] - m + AT_FRAC));
+  red[t] = o;
+  __syncthreads();
+  if (t < D) {
+    int sum = 0;
+    for (int sl = 0; sl < slices; ++sl) sum += red[sl * D + t];
+    ofix[(hbase + i) * D + t] = sum;
+  }
+}
+
+// f32_int with an exponent offset: the float times 2^frac_bits as an integer, by bit pattern.
+// False when it is no such multiple of magnitude below 2^31: a finer fraction, an infinity, a NaN.
+__device__ static inline bool f32_fixed(uint32_t bits, int frac_bits, int* out) {
+  const int e = (bits >> 23) & 0xff;
+  const uint32_t frac = bits & 0x7fffffu;
+  *out = 0;
+  if (e == 0) return frac == 0;            // +-0; a subnormal is a fraction
+  const int up = e - 150 + frac_bits;       // the scaled value is sig * 2^up
+  if (up > 7 || up < -23) return false;     // 2^31 and above, infinity, NaN; below one unit
+  const uint32_t sig = 0x800000u | frac;
+  if (up < 0 && (sig & ((1u << -up) - 1u))) return false;
+  const int mag = static_cast<int>(up < 0 ? sig >> -up : sig << up);
+  *out = (bits >> 31) ? -mag : mag;
+  return true;
+}
+
+struct AttnRecord {
+  int kind;  // 0 "o", 1 "l", 2 "m"
+  int head, i, c, delta;
+};
+struct AttnResult {
+  unsigned int count, no, nml;
+  AttnRecord o[MAX_RECORDS], ml[MAX_RECORDS];  // the first few wrong O' elements, the first few wrong l or m
+};
+
+// Every fp32 of O' (H S d of them) and of ML (H S pairs m, l) against its integer in units of
+// 2^-12, with ==.  The delta of a record is in those units, CU_NOT_INT for a value that is no
+// multiple of the unit.
+__global__ __launch_bounds__(256) void verify_attn_kernel(const float* __restrict__ O, const int* __restrict__ ofix,
+                                                          const float* __restrict__ ML, const int* __restrict__ mlfix,
+                                                          size_t no, size_t nml, int S, int D, AttnResult* res) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t x = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; x < no + nml; x += stride) {
+    const bool is_o = x < no;
+    const size_t y = is_o ? x : x - no;
+    const int want = is_o ? ofix[y] : mlfix[y];
+    int have;
+    const bool whole = f32_fixed(__float_as_uint(is_o ? O[y] : ML[y]), AT_FRAC, &have);
+    if (whole && have == want) continue;
+    atomicAdd(&res->count, 1u);
+    const unsigned int slot = atomicAdd(is_o ? &res->no : &res->nml, 1u);
+    if (slot < MAX_RECORDS) {
+      const size_t row = is_o ? y / D : y / 2;
+      const AttnRecord rec = {is_o ? 0 : (y & 1) ? 1 : 2, static_cast<int>(row / S), static_cast<int>(row % S),
+                              is_o ? static_cast<int>(y % D) : 0, whole ? have - want : CU_NOT_INT};
+      (is_o ? res->o : res->ml)[slot] = rec;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // Host
 // ------------------------------------------------------------------------------------------
 
@@ -1635,7 +2061,10 @@ static int usage(const char* why) {
           "65536; --a/--b hold raw int8 bytes, every value valid\n       gpu_check hbm --mib SIZE [--passes P] [--seed S] [--flip WORD:MASK] "
           "[--device D]\n       gpu_check cu [--k K] [--reps R] [--passes P] [--rounds N] [--seed S] [--flip WG:WORD:MASK] "
           "[--poison WG:WAVE:I,J] [--device D]\n         K a multiple of 16 and at most 304, what 16 waves' operands take of "
-          "the 160 KB of LDS; WORD below 40960, WAVE below 16, I,J inside 32x32\n",
+          "the 160 KB of LDS; WORD below 40960, WAVE below 16, I,J inside 32x32\n       gpu_check attn [--heads H] [--seq S] "
+          "[--d 64|128] [--causal] [--seed S] [--seconds T] [--q FILE --k FILE --v FILE] [--o-out FILE] [--ml-out FILE] "
+          "[--poison H,I,C] [--device D]\n         defaults: 64 heads, S 2048, d 128, not causal; S a multiple of 64 and at most "
+          "2048; K and V hold integers in [-2, 2], every Q row integers with sum |q| <= 3\n",
           why);
   return 2;
 }
@@ -2067,12 +2496,138 @@ static int run_cu(CuArgs a, int rounds, int device) {
   return ok ? 0 : 1;
 }
 
+// rows x D raw little-endian bf16 of Q: every element an integer, every row's magnitudes summing to at most 3
+static bool read_q(const std::string& path, size_t rows, int D, std::vector<uint16_t>* out) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return false;
+  out->resize(rows * D);
+  const size_t got = fread(out->data(), 2, out->size(), f);
+  const bool exact = got == out->size() && fgetc(f) == EOF;
+  fclose(f);
+  if (!exact) return false;
+  for (size_t r = 0; r < rows; ++r) {
+    int sum = 0;
+    for (int c = 0; c < D; ++c) {
+      int v;
+      if (!bf16_whole((*out)[r * D + c], &v)) return false;
+      sum += v < 0 ? -v : v;
+    }
+    if (sum > 3) return false;
+  }
+  return true;
+}
+
+static bool write_file(const std::string& path, const void* dev, size_t bytes) {
+  std::vector<unsigned char> h(bytes);
+  CHECK(hipMemcpy(h.data(), dev, bytes, hipMemcpyDeviceToHost));
+  FILE* f = fopen(path.c_str(), "wb");
+  const bool ok = f && fwrite(h.data(), 1, bytes, f) == bytes;
+  if (f) fclose(f);
+  return ok;
+}
+
+static int run_attn(int H, int S, int D, bool causal, uint32_t seed, const std::string& q_file, const std::string& k_file,
+                    const std::string& v_file, const std::string& o_out, const std::string& ml_out, int poison_h,
+                    int poison_i, int poison_c, int device, double seconds) {
+  // the caps of the exactness argument in the header: 2 S 2^12 <= 2^24
+  if (S <= 0 || S % AT_KEYS || S > AT_S_CAP || (D != 64 && D != 128) || H < 1 || H > 65535)
+    return usage("attn: S must be a multiple of 64 and at most 2048, d 64 or 128, H from 1 to 65535 (attn)");
+  if (q_file.empty() != k_file.empty() || q_file.empty() != v_file.empty()) return usage("attn: --q, --k and --v go together (attn)");
+  if (poison_h >= H || poison_i >= S || poison_c >= D) return usage("attn: --poison outside O' (attn)");
+  const size_t rows = static_cast<size_t>(H) * S, elems = rows * D;
+  std::vector<uint16_t> hq, hk, hv;
+  if (!q_file.empty() && !(read_q(q_file, rows, D, &hq) && read_operand(k_file, elems, &hk) && read_operand(v_file, elems, &hv)))
+    return usage("attn: --q/--k/--v must hold exactly H*S*d bf16 each: K and V integers in [-2, 2], every row of Q integers "
+                 "whose magnitudes sum to at most 3 (attn)");
+
+  CHECK(hipSetDevice(device));
+  const int grid = grid_for(device);
+  uint16_t *Q = nullptr, *K = nullptr, *V = nullptr;
+  float *O = nullptr, *ML = nullptr;
+  int *ofix = nullptr, *mlfix = nullptr;
+  AttnResult* res = nullptr;
+  CHECK(hipMalloc(&Q, elems * 2));
+  CHECK(hipMalloc(&K, elems * 2));
+  CHECK(hipMalloc(&V, elems * 2));
+  CHECK(hipMalloc(&O, elems * 4));
+  CHECK(hipMalloc(&ML, rows * 2 * 4));
+  CHECK(hipMalloc(&ofix, elems * 4));
+  CHECK(hipMalloc(&mlfix, rows * 2 * 4));
+  CHECK(hipMalloc(&res, sizeof(AttnResult)));
+  if (!q_file.empty()) {
+    CHECK(hipMemcpy(Q, hq.data(), elems * 2, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(K, hk.data(), elems * 2, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(V, hv.data(), elems * 2, hipMemcpyHostToDevice));
+  } else {
+    hipLaunchKernelGGL(generate_q_kernel, dim3(grid), dim3(256), 0, 0, Q, rows, D, mix32(3 * seed));
+    hipLaunchKernelGGL(generate_kernel, dim3(grid), dim3(256), 0, 0, K, static_cast<int>(rows), D, mix32(3 * seed + 1));
+    hipLaunchKernelGGL(generate_kernel, dim3(grid), dim3(256), 0, 0, V, static_cast<int>(rows), D, mix32(3 * seed + 2));
+  }
+  // the inputs are the same in every pass, so the expectation is computed once
+  hipLaunchKernelGGL(expect_attn_kernel, dim3(S, H), dim3(256), 0, 0, Q, K, V, S, D, causal ? 1 : 0, ofix, mlfix);
+  CHECK(hipGetLastError());
+  hipEvent_t ev0, ev1;
+  CHECK(hipEventCreate(&ev0));
+  CHECK(hipEventCreate(&ev1));
+
+  AttnResult host = {};
+  int passes = 0;
+  double attn_ms = 0.0;
+  const dim3 blocks((S + AT_QROWS - 1) / AT_QROWS, H);
+  const auto t0 = std::chrono::steady_clock::now();
+  do {
+    CHECK(hipMemset(res, 0, sizeof(AttnResult)));
+    CHECK(hipEventRecord(ev0));
+    if (D == 64 && !causal) hipLaunchKernelGGL((attn_kernel<64, false>), blocks, dim3(256), 0, 0, Q, K, V, S, O, ML, poison_h, poison_i, poison_c);
+    else if (D == 64) hipLaunchKernelGGL((attn_kernel<64, true>), blocks, dim3(256), 0, 0, Q, K, V, S, O, ML, poison_h, poison_i, poison_c);
+    else if (!causal) hipLaunchKernelGGL((attn_kernel<128, false>), blocks, dim3(256), 0, 0, Q, K, V, S, O, ML, poison_h, poison_i, poison_c);
+    else hipLaunchKernelGGL((attn_kernel<128, true>), blocks, dim3(256), 0, 0, Q, K, V, S, O, ML, poison_h, poison_i, poison_c);
+    CHECK(hipEventRecord(ev1));
+    hipLaunchKernelGGL(verify_attn_kernel, dim3(grid), dim3(256), 0, 0, O, ofix, ML, mlfix, elems, rows * 2, S, D, res);
+    CHECK(hipGetLastError());
+    CHECK(hipMemcpy(&host, res, sizeof(AttnResult), hipMemcpyDeviceToHost));
+    float ms = 0.0f;
+    CHECK(hipEventElapsedTime(&ms, ev0, ev1));
+    attn_ms += ms;
+    ++passes;
+  } while (host.count == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < seconds);
+
+  if (!o_out.empty() && !write_file(o_out, O, elems * 4)) return usage("attn: cannot write --o-out (attn)");
+  if (!ml_out.empty() && !write_file(ml_out, ML, rows * 2 * 4)) return usage("attn: cannot write --ml-out (attn)");
+  const bool ok = host.count == 0;
+  // wrong O' elements first, then l and m, each list in index order (the slots were taken in any order)
+  const auto before = [](const AttnRecord& a, const AttnRecord& b) {
+    return a.head != b.head ? a.head < b.head : a.i != b.i ? a.i < b.i : a.c != b.c ? a.c < b.c : a.kind < b.kind;
+  };
+  const unsigned int no = std::min(host.no, static_cast<unsigned int>(MAX_RECORDS));
+  const unsigned int nml = std::min(host.nml, static_cast<unsigned int>(MAX_RECORDS) - no);
+  std::sort(host.o, host.o + no, before);
+  std::sort(host.ml, host.ml + std::min(host.nml, static_cast<unsigned int>(MAX_RECORDS)), before);
+  std::string recs;
+  for (unsigned int r = 0; r < no + nml; ++r) {
+    const AttnRecord& a = r < no ? host.o[r] : host.ml[r - no];
+    char buf[160];
+    snprintf(buf, sizeof buf, "{\"kind\":\"%s\",\"head\":%d,\"i\":%d,\"c\":%d,\"delta\":%d}", a.kind == 0 ? "o" : a.kind == 1 ? "l" : "m",
+             a.head, a.i, a.c, a.delta);
+    recs += (r ? "," : "") + std::string(buf);
+  }
+  const double flops = 4.0 * S * S * D * H * (causal ? 0.5 : 1.0);
+  printf("{\"check\":\"attn\",\"ok\":%s,\"heads\":%d,\"seq\":%d,\"d\":%d,\"causal\":%s,\"passes\":%d,\"mismatch_count\":%u,"
+         "\"mismatches\":[%s],\"tflops\":%.3f}\n",
+         ok ? "true" : "false", H, S, D, causal ? "true" : "false", passes, host.count, recs.c_str(),
+         attn_ms > 0 ? flops * passes / (attn_ms * 1e-3) / 1e12 : 0.0);
+  return ok ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return usage("a subcommand is needed");
   const std::string mode = argv[1];
-  if (mode != "gemm" && mode != "hbm" && mode != "cu") return usage("unknown subcommand");
-  g_check = mode == "gemm" ? "gemm" : mode == "hbm" ? "hbm" : "cu";
-  const bool cu = mode == "cu";
+  if (mode != "gemm" && mode != "hbm" && mode != "cu" && mode != "attn") return usage("unknown subcommand");
+  g_check = mode == "gemm" ? "gemm" : mode == "hbm" ? "hbm" : mode == "cu" ? "cu" : "attn";
+  const bool cu = mode == "cu", attn = mode == "attn";
+  int heads = 64, seq = AT_S_CAP, head_dim = 128, poison_h = -1, poison_c = -1;  // attn only
+  bool causal = false;
+  std::string q_file, k_file, v_file, o_out, ml_out;
   int fmt = BF16, M = 8192, N = 8192, K = 0, device = 0, passes = cu ? 4 : 2, poison_i = -1, poison_j = -1;
   int reps = 16, rounds = 8, flip_wg = -1, poison_wg = -1, poison_wave = 0;  // cu only
   double seconds = 2.0, mib = 0.0;
@@ -2082,10 +2637,37 @@ int main(int argc, char** argv) {
   std::string a_file, b_file, sa_file, sb_file, c_out;
   for (int i = 2; i < argc; i += 2) {
     const std::string k = argv[i];
+    if (attn && k == "--causal") {  // the one option without a value
+      causal = true;
+      --i;
+      continue;
+    }
     if (i + 1 >= argc) return usage(("option " + k + " needs a value").c_str());
     const char* v = argv[i + 1];
     char* end = nullptr;
     const bool gemm = mode == "gemm";
+    if (attn) {
+      if (k == "--device") device = atoi(v);
+      else if (k == "--seed") seed = static_cast<uint32_t>(strtoul(v, nullptr, 0));
+      else if (k == "--seconds") seconds = atof(v);
+      else if (k == "--heads") heads = atoi(v);
+      else if (k == "--seq") seq = atoi(v);
+      else if (k == "--d") head_dim = atoi(v);
+      else if (k == "--q") q_file = v;
+      else if (k == "--k") k_file = v;
+      else if (k == "--v") v_file = v;
+      else if (k == "--o-out") o_out = v;
+      else if (k == "--ml-out") ml_out = v;
+      else if (k == "--poison") {
+        poison_h = static_cast<int>(strtol(v, &end, 10));
+        if (*end != ',' || poison_h < 0) return usage("--poison wants H,I,C (attn)");
+        poison_i = static_cast<int>(strtol(end + 1, &end, 10));
+        if (*end != ',' || poison_i < 0) return usage("--poison wants H,I,C (attn)");
+        poison_c = static_cast<int>(strtol(end + 1, &end, 10));
+        if (*end != '\0' || poison_c < 0) return usage("--poison wants H,I,C (attn)");
+      } else return usage(("unknown option " + k + " (attn)").c_str());
+      continue;
+    }
     if (k == "--device") device = atoi(v);
     else if (k == "--seed") seed = static_cast<uint32_t>(strtoul(v, nullptr, 0));
     else if (cu && k == "--reps") reps = atoi(v);
@@ -2140,6 +2722,9 @@ int main(int argc, char** argv) {
     } else return usage(("unknown option " + k).c_str());
   }
   if (device < 0) return usage("--device must not be negative");
+  if (attn)
+    return run_attn(heads, seq, head_dim, causal, seed, q_file, k_file, v_file, o_out, ml_out, poison_h, poison_i, poison_c,
+                    device, seconds);
   if (cu) {
     flip_word = std::min(flip_word, static_cast<unsigned long long>(CU_LDS_WORDS));  // a word past the LDS is refused below
     const CuArgs a = {seed,      passes,    K == 0 ? CU_K_CAP : K, reps,    flip_wg, static_cast<int>(flip_word),

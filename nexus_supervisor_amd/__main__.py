@@ -10,7 +10,8 @@
 ``build``       build the native components in-tree
 ``cqlsrv``      run the native in-memory CQL server (tests / local runs)
 ``gpu-check``   ask one GPU whether it is bad: known-answer MFMA GEMM + HBM pattern test
-                (``--device D``, ``--quick``, ``--per-cu``, ``--json``; exit 1 when a check fails)
+                (``--device D``, ``--quick``, ``--per-cu``, ``--attention``, ``--json``; exit 1 when a
+                check fails)
 ``version``     print the version
 """
 from __future__ import annotations
@@ -84,11 +85,13 @@ def main(argv=None) -> int:
         ap.add_argument("--dtypes", default="bf16", help="GEMM formats, comma-separated: bf16[,mxfp8][,mxfp4][,fp64][,int8]")
         ap.add_argument("--all-formats", action="store_true", help="the same as --dtypes bf16,mxfp8,mxfp4; for FP64 or INT8 name it: --dtypes bf16,fp64,int8")
         ap.add_argument("--per-cu", action="store_true", help="also check every CU's LDS and matrix units, named by XCC, SE and CU")
+        ap.add_argument("--attention", action="store_true",
+                        help="also run a known-answer fused attention (QK^T, exp2 softmax, PV); its final division is not covered")
         a = ap.parse_args(argv)
         quick = {"gemm": (1024, 1024, 1024), "seconds": 0.0, "hbm_mib": 256.0} if a.quick else {}
         dtypes = ("bf16", "mxfp8", "mxfp4") if a.all_formats else tuple(a.dtypes.split(","))
         try:
-            result = check_gpu(a.device, dtypes=dtypes, cu=a.per_cu, **quick)
+            result = check_gpu(a.device, dtypes=dtypes, cu=a.per_cu, attn=a.attention, **quick)
         except ValueError as e:
             ap.error(str(e))
         print(json.dumps(result) if a.json else summarize(result))

@@ -13,6 +13,10 @@ check whose operands toggle every bit.
 Also on request, ``gpu_check cu`` says where on the die: one workgroup per compute unit sweeps that
 CU's whole 160 KB of LDS and runs a known-answer matrix chain on each of its SIMDs, and a fault is
 named by XCC, shader engine and CU, which in CPX mode is one partition and not the whole OAM.
+Also on request, ``gpu_check attn`` runs a known-answer fused attention (QK^T, a base-2 online
+softmax, PV): matrix accumulators fed back to the matrix unit as operands without leaving the
+registers, cross-lane row reductions, ``v_exp_f32``, the fp32 -> bf16 pack, the rescale of live
+accumulators.  Small integer scores make every probability a power of two, so this one is exact too.
 
 The checks run as child processes, one after the other.  The caller (a long-lived agent)
 never opens the GPU itself, so it never shows in amd-smi's process list, and a child that
@@ -63,7 +67,8 @@ EXTRA_K_CAP = {**MX_K_CAP, "fp64": 8192, "int8": 65536}
 
 def check_gpu(device: int = 0, *, gemm: Sequence[int] = (8192, 8192, 4096), seconds: float = 2.0,
               hbm_mib: Optional[float] = None, passes: int = 2, timeout: float = 120.0,
-              binary: Optional[str] = None, dtypes: Sequence[str] = ("bf16",), cu: bool = False) -> Dict[str, Any]:
+              binary: Optional[str] = None, dtypes: Sequence[str] = ("bf16",), cu: bool = False,
+              attn: bool = False) -> Dict[str, Any]:
     """Run the GEMM check, then the HBM check, on ``device``.  ``hbm_mib=None`` lets the
     binary size the sweep (the smaller of 32 GiB and half of what is free); ``binary``
     overrides the built ``bin/gpu_check``.  ``dtypes`` names the GEMM formats: ``"bf16"``
@@ -72,7 +77,9 @@ def check_gpu(device: int = 0, *, gemm: Sequence[int] = (8192, 8192, 4096), seco
     ``EXTRA_K_CAP``, its record under ``"gemm_mxfp8"`` / ``"gemm_mxfp4"`` / ``"gemm_fp64"`` /
     ``"gemm_int8"``.  ``cu=True`` adds the
     per-CU check (``gpu_check cu``: each compute unit's whole LDS and the matrix unit of each of
-    its SIMDs, named by XCC, SE and CU) after the GEMM children, its record under ``"cu"``.  Returns
+    its SIMDs, named by XCC, SE and CU) after the GEMM children, its record under ``"cu"``.
+    ``attn=True`` adds the fused-attention check (``gpu_check attn`` at its defaults, for ``seconds``)
+    after the GEMM children and before the per-CU one, its record under ``"attn"``.  Returns
     ``{"ok", "device", "gemm", "hbm", "elapsed_s", "error"}`` and those: ``ok`` only if every
     child exited 0 and said ok; ``error`` names the steps that failed and how.  After a step
     that ended by signal or timeout nothing more is started: the rest is ``{"skipped": True}``."""
@@ -89,12 +96,13 @@ def check_gpu(device: int = 0, *, gemm: Sequence[int] = (8192, 8192, 4096), seco
                   "--device", str(device)]),
         *((f"gemm_{d}", [binary, "gemm", "--dtype", d, "--m", str(m), "--n", str(n), "--k", str(min(k, EXTRA_K_CAP[d])),
                          "--seconds", repr(float(seconds)), "--device", str(device)]) for d in extra),
+        *([("attn", [binary, "attn", "--seconds", repr(float(seconds)), "--device", str(device)])] if attn else []),
         *([("cu", [binary, "cu", "--device", str(device)])] if cu else []),
         ("hbm", [binary, "hbm", "--passes", str(passes), "--device", str(device)]
          + (["--mib", repr(float(hbm_mib))] if hbm_mib is not None else [])),
     ]
     out: Dict[str, Any] = {"ok": True, "device": device, "gemm": {}, **{f"gemm_{d}": {} for d in extra},
-                           **({"cu": {}} if cu else {}), "hbm": {},
+                           **({"attn": {}} if attn else {}), **({"cu": {}} if cu else {}), "hbm": {},
                            "elapsed_s": 0.0, "error": None}
     errors = []
     t0 = time.monotonic()
@@ -127,6 +135,22 @@ def _gemm_text(rec: Dict[str, Any], label: str = "gemm") -> str:
              "column": "column {j} (row stripe {stripe})"}.get(first.get("kind"), "?")
     text = f"{label} mismatch at {where.format(**first)} ({delta:+g}) in tile {first.get('tile')}"
     return text + (f" and {len(mm) - 1} more" if len(mm) > 1 else "")
+
+
+def _attn_text(rec: Dict[str, Any]) -> str:
+    if rec.get("skipped"):
+        return "attn not run"
+    if rec.get("ok") is True:
+        return "attn clean"
+    mm = rec.get("mismatches") or []
+    if not mm:
+        return "attn failed"
+    first = mm[0]
+    where = {"o": "O[{i},{c}]", "l": "l[{i}]", "m": "m[{i}]"}.get(first.get("kind"), "?").format(**first)
+    delta = first.get("delta", 0)  # in units of 2^-12; INT32_MIN marks a value that is no multiple of the unit
+    size = "not a multiple of 2^-12" if delta == -2 ** 31 else f"{delta:+d} x 2^-12"
+    more = rec.get("mismatch_count", len(mm)) - 1
+    return f"attn mismatch at head {first.get('head')} {where} ({size})" + (f" and {more} more" if more > 0 else "")
 
 
 def _cu_text(rec: Dict[str, Any]) -> str:
@@ -172,6 +196,8 @@ def summarize(result: Dict[str, Any]) -> str:
     ``gpu 0: gemm mismatch at C[37,101] (+1) in tile 0; hbm clean``."""
     parts = [_gemm_text(result.get("gemm") or {})]
     parts += [_gemm_text(result[f"gemm_{d}"] or {}, f"gemm {d}") for d in EXTRA_K_CAP if f"gemm_{d}" in result]
+    if "attn" in result:
+        parts.append(_attn_text(result["attn"] or {}))
     if "cu" in result:
         parts.append(_cu_text(result["cu"] or {}))
     text = f"gpu {result.get('device')}: {'; '.join(parts)}; {_hbm_text(result.get('hbm') or {})}"
